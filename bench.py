@@ -7,11 +7,17 @@ GPU per step (data parallel, weak scaling).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run only sets up, warms up, times the --steps
+steps and reports them (`roofline` and `cpu_baseline` are null).  `--full` adds everything else, each measured after the
+headline steps:
   roofline     - the dominant GEMM kernel's achieved TFLOP/s (algorithmic FLOPs / HIP-event time of its launches in the
                  timed region) against the dense f32-input MFMA peak;
   cpu_baseline - the CPU oracle (oracle/phnet_cpu.py, a restatement of the reference's PyTorch-CPU path) timed on this
-                 box's host cores on a bounded sample of the same workload.
+                 box's host cores on a bounded sample of the same workload;
+  batched, f32_mfma, inference - the same step with several clips per GPU, the step on the f32-input MFMA, and the
+                 inference workload (BASELINE.json configs[4]), each in a child process.
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32; see dump_outputs).
 """
 import argparse
 import json
@@ -76,12 +82,18 @@ def parse():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=800)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the roofline (kernel timer), the CPU baseline and the extras "
+                         "(--batched-extra, --split-extra, --inference-extra); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss; seeded samples of the updated parameters, "
+                         "their gradients and the floating-point buffers) as DIR/<name>.npy")
     ap.add_argument("--clips-per-gpu", type=int, default=1,
                     help="clips per GPU and step (default 1 = BASELINE.json configs[1], the reference's train_batch).  B > 1 runs "
                          "the lane head batched across the clips with joint BatchNorm statistics = the reference's DDP + "
                          "SyncBatchNorm over B virtual ranks on one GPU; a different workload, reported as such")
     ap.add_argument("--batched-extra", type=int, default=8,
-                    help="N = 1 only: after the headline measurement, also time B clips per GPU and step in a child process and "
+                    help="--full, N = 1 only: after the headline measurement, also time B clips per GPU and step in a child process and "
                          "report it under the extra key 'batched' (0 = skip)")
     ap.add_argument("--mma", default="bf16x3", choices=["f32", "split_bf16", "split3_bf16", "bf16x3"],
                     help="arithmetic of the conv / linear GEMM kernels: bf16x3 (default, the headline: f32 operands split EXACTLY "
@@ -89,10 +101,10 @@ def parse():
                          "accuracy of the f32-input MFMA), f32 (v_mfma_f32_32x32x2_f32, the round-1 headline), or the two-term "
                          "split_bf16 (3 MFMAs per product, ~4x the rounding noise: not parity-grade)")
     ap.add_argument("--split-extra", type=int, default=1,
-                    help="after the headline run, also time the step on the f32-input MFMA (the round-1 arithmetic) and report it "
+                    help="--full: after the headline run, also time the step on the f32-input MFMA (the round-1 arithmetic) and report it "
                          "under the extra key 'f32_mfma' (0 = skip)")
     ap.add_argument("--inference-extra", type=int, default=1,
-                    help="N = 1 only: also run the inference workload of BASELINE.json configs[4] (32 clips x 5 frames, lane head + "
+                    help="--full, N = 1 only: also run the inference workload of BASELINE.json configs[4] (32 clips x 5 frames, lane head + "
                          "fused decode / NMS, hipGraph) in a child process and report it under the extra key 'inference' (0 = skip)")
     ap.add_argument("--inference", action="store_true", help="run ONLY the inference workload and print its JSON (used by the child)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -117,7 +129,42 @@ def parse():
                     help="rehearsal on ONE GPU: run the N > 1 code path (SyncBatchNorm containers, bucket reducer, RCCL collectives captured "
                          "in the graph) in a one-rank process group with the collectives forced on - what the data-parallel machinery "
                          "costs per step before any link is involved")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22                 # elements per dumped array at most: three arrays of 16 MB stay under 64 MB in all
+
+
+def dump_outputs(out_dir, model, loss):
+    """What the timed step hands its caller, from the last timed step: the loss it returned (per rank, before the world-size
+    scaling of the result line) and the state its AdamW update and BatchNorm statistics left behind - the parameters, their
+    gradients and the floating-point buffers.  Each of the last three is the concatenation of the tensors in
+    named_parameters() / named_buffers() order, every tensor flattened in its logical (NCHW) element order whatever its
+    memory layout, so that builds with other arena layouts still compare element for element; above DUMP_SAMPLE elements
+    a fixed, seeded sample of positions (the same for every run of the same model) is kept, in ascending order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(ts):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.cpu().numpy()
+
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params": sample(params),
+              "grads": sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]),
+              "buffers": sample([b for b in model.buffers() if b.is_floating_point()])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+    print(f"[bench] outputs of the last timed step written to {out_dir}: "
+          + ", ".join(f"{k} {v.size}" for k, v in arrays.items()), file=sys.stderr, flush=True)
 
 
 def cpu_baseline(args):
@@ -395,7 +442,8 @@ def main():
         print(f"[bench] rank {rank} warm-up step {i + 1}/{args.warmup} done", file=sys.stderr, flush=True)
     if world > 1:
         dist.barrier()
-    timer_on = not args.no_kernel_timer and graphed is None
+    kernel_timer = args.full and not args.no_kernel_timer
+    timer_on = kernel_timer and graphed is None
     if timer_on:
         hip_ops.TIMER = []
     torch.cuda.synchronize()
@@ -411,9 +459,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)          # the job's time is its slowest rank's
     dt = float(tmax.item())
     records, hip_ops.TIMER = hip_ops.TIMER, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)             # before anything below runs another step
     timer_note = "HIP events around every launch of the kernel inside the timed region (eager)"
     isolated = None
-    if graphed is not None and not args.no_kernel_timer:
+    if graphed is not None and kernel_timer:
         # Launches inside a graph replay cannot be bracketed by events (hipEventRecord nodes carry no timestamps on
         # ROCm 7.2).  Instead: run ONE instrumented eager step right after the timed region to collect every GEMM launch
         # of a step (same kernels, same shapes, same buffers), then re-issue those launches grouped by kernel symbol
@@ -499,10 +549,10 @@ def main():
                     "gemm_ms_per_step": round(total_gemm_s / steps_timed * 1e3, 3), "timing": timer_note,
                     "backbone_conv_mfma_util_pct": mfma_util}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args)
         batched = None
-        if world == 1 and CB == 1 and args.batched_extra > 1 and use_graph:
+        if args.full and world == 1 and CB == 1 and args.batched_extra > 1 and use_graph:
             batched = batched_extra(args)
         out = {"metric": f"clips/s ({T}x3x{args.height}x{args.width}) fwd+bwd", "value": round(world * CB * args.steps / dt, 4), "unit": "clips/s",
                "n_gpus": dist.get_world_size() if dp else 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -518,11 +568,11 @@ def main():
                "loss": round(float(loss.item()) * world, 4), "roofline": roof, "cpu_baseline": cpu}
         if batched is not None:
             out["batched"] = batched
-        if world == 1 and CB == 1 and args.split_extra and use_graph and args.mma != "f32":
+        if args.full and world == 1 and CB == 1 and args.split_extra and use_graph and args.mma != "f32":
             sp = f32_extra(args)
             if sp is not None:
                 out["f32_mfma"] = sp
-        if world == 1 and CB == 1 and args.inference_extra:
+        if args.full and world == 1 and CB == 1 and args.inference_extra:
             inf = inference_extra(args)
             if inf is not None:
                 out["inference"] = inf

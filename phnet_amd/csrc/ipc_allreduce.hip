@@ -15,24 +15,29 @@
 // sequence n+1 from every peer knows that every peer has finished reading sequence n, so slot (n+2) & 1 is free again.
 // The sequence number lives in device memory and is advanced by the kernel itself (one workgroup per call): a hipGraph replay of
 // the step keeps counting.
-// Every spin is bounded: a peer that never arrives raises `*err` and the wave leaves (no hang, the result is then invalid).
+// Every spin is bounded in wall-clock time (IPC_TIMEOUT_S on the GPU's constant-rate clock, not a poll count: a poll costs
+// far less than a microsecond, and a peer that is merely late - another process, started and scheduled on its own - must not
+// count as lost): a peer that never arrives raises `*err` and the wave leaves (no hang, the result is then invalid).  Once
+// `*err` is set, later calls do not wait again.
 #include "common.h"
 
 namespace {
 
 constexpr int IPC_NT = 1024;                                       // ONE workgroup per call: the messages are <= 1025 elements
-constexpr unsigned long long IPC_MAX_POLLS = 1ull << 21;          // x ~1 us per poll: seconds, then give up
+constexpr int IPC_TIMEOUT_S = 30;                                 // a peer this late is lost
 
 // buf layout (per rank): [2 slots][world][cap] granules of 8 bytes; ctrl: {uint32 seq, uint32 err}
 template <typename T>
 __global__ __launch_bounds__(IPC_NT) void oneshot_allreduce_kernel(T* __restrict__ data, int count, unsigned long long* const* __restrict__ peers,
-                                                                   int rank, int world, int cap, unsigned* __restrict__ ctrl)
+                                                                   int rank, int world, int cap, unsigned* __restrict__ ctrl,
+                                                                   unsigned long long max_ticks)
 {
     constexpr int G = sizeof(T) / 4;                               // granules per element
     const unsigned seq = ctrl[0];
     __syncthreads();                                               // everybody holds the sequence number before thread 0 advances it
     const size_t slot = (size_t)(seq & 1u) * world * cap;
-    bool timed_out = false;
+    bool timed_out = ctrl[1] != 0u;                                // an earlier exchange already lost a peer: do not wait again
+    const unsigned long long t0 = wall_clock64();
     for (int k = threadIdx.x; k < count; k += IPC_NT) {
         unsigned w[G];
         __builtin_memcpy(w, &data[k], sizeof(T));
@@ -53,11 +58,10 @@ __global__ __launch_bounds__(IPC_NT) void oneshot_allreduce_kernel(T* __restrict
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 unsigned long long v = 0;
-                unsigned long long polls = 0;
                 for (;;) {
                     v = __hip_atomic_load(mine + (size_t)p * cap + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     if ((unsigned)(v >> 32) == seq) break;
-                    if (timed_out || ++polls > IPC_MAX_POLLS) { timed_out = true; break; }
+                    if (timed_out || wall_clock64() - t0 > max_ticks) { timed_out = true; break; }
                     __builtin_amdgcn_s_sleep(2);
                 }
                 r[g] = (unsigned)v;
@@ -126,12 +130,21 @@ PHNET_API int phnet_oneshot_allreduce(void* data, int32_t count, int32_t dtype, 
 {
     if (!data || !peers || !ctrl || count < 1 || world < 1 || rank < 0 || rank >= world || (dtype != 0 && dtype != 1)) return PHNET_ERR_ARG;
     if ((long)count * (dtype ? 2 : 1) > cap) return PHNET_ERR_WORKSPACE;
+    static unsigned long long max_ticks = 0;                       // IPC_TIMEOUT_S in ticks of wall_clock64()
+    if (max_ticks == 0) {
+        int dev = 0, khz = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) {
+            (void)hipGetLastError();
+            khz = 100000;                                          // the 100 MHz constant clock of gfx9 parts
+        }
+        max_ticks = (unsigned long long)khz * 1000ull * IPC_TIMEOUT_S;
+    }
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 1)
         hipLaunchKernelGGL(oneshot_allreduce_kernel<double>, dim3(1), dim3(IPC_NT), 0, st, (double*)data, count,
-                           (unsigned long long* const*)peers, rank, world, cap, (unsigned*)ctrl);
+                           (unsigned long long* const*)peers, rank, world, cap, (unsigned*)ctrl, max_ticks);
     else
         hipLaunchKernelGGL(oneshot_allreduce_kernel<float>, dim3(1), dim3(IPC_NT), 0, st, (float*)data, count,
-                           (unsigned long long* const*)peers, rank, world, cap, (unsigned*)ctrl);
+                           (unsigned long long* const*)peers, rank, world, cap, (unsigned*)ctrl, max_ticks);
     return phnet_launch_status();
 }

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_pool_fwd_any_kernel(
 
 __global__ __launch_bounds__(ROI_THREADS) void roi_pool_bwd_kernel(
     const float* __restrict__ dout, const float* __restrict__ fmap, const float* __restrict__ xs,
-    const float* __restrict__ ys, float* __restrict__ dmap, float* __restrict__ dxs,
-    int B, int N, int P, int h, int w)
+    const float* __restrict__ ys, float* __restrict__ dxs, int B, int N, int P, int h, int w)
 {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * (ROI_THREADS / 64) + (threadIdx.x >> 6);
@@ -136,29 +135,100 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_pool_bwd_kernel(
         const float ye = fy + 1.0f;
         if (y0in && x0in) {
             const size_t o = plane + ((size_t)c.y0 * w + c.x0) * ROI_C;
-            if (dmap) atomicAdd(dmap + o, g * c.nw);
-            if (dxs) gix -= fmap[o] * (ye - c.iy) * g;
+            gix -= fmap[o] * (ye - c.iy) * g;
         }
         if (y0in && x1in) {
             const size_t o = plane + ((size_t)c.y0 * w + c.x0 + 1) * ROI_C;
-            if (dmap) atomicAdd(dmap + o, g * c.ne);
-            if (dxs) gix += fmap[o] * (ye - c.iy) * g;
+            gix += fmap[o] * (ye - c.iy) * g;
         }
         if (y1in && x0in) {
             const size_t o = plane + ((size_t)(c.y0 + 1) * w + c.x0) * ROI_C;
-            if (dmap) atomicAdd(dmap + o, g * c.sw);
-            if (dxs) gix -= fmap[o] * (c.iy - fy) * g;
+            gix -= fmap[o] * (c.iy - fy) * g;
         }
         if (y1in && x1in) {
             const size_t o = plane + ((size_t)(c.y0 + 1) * w + c.x0 + 1) * ROI_C;
-            if (dmap) atomicAdd(dmap + o, g * c.se);
-            if (dxs) gix += fmap[o] * (c.iy - fy) * g;
+            gix += fmap[o] * (c.iy - fy) * g;
         }
     }
-    if (dxs) {
-        gix = wave_sum(gix);
-        // d(ix)/d(g) = (w-1)/2 and g = 2*x-1
-        if (lane == 0) dxs[bn * P + (P - 1 - k)] = gix * ((float)(w - 1) / 2.0f) * 2.0f;
+    gix = wave_sum(gix);
+    // d(ix)/d(g) = (w-1)/2 and g = 2*x-1
+    if (lane == 0) dxs[bn * P + (P - 1 - k)] = gix * ((float)(w - 1) / 2.0f) * 2.0f;
+}
+
+// Map gradient as a GATHER, so that every run sums in the same order (float atomics made the training step differ from run
+// to run).  One workgroup per map pixel (b, y, x), lane = channel.  The row of point k depends on ys[k] only, so a wave
+// first ballots the points whose corner rows touch y, then, per such k, the anchors whose corner columns touch x; wave v
+// takes the anchors n = v*64 + 256*i + lane.  Each wave sums its matches in ascending (k, n) order (dout loads issued 8
+// at a time); the four partial sums are added in wave order and the total is added to dmap once.
+constexpr int ROI_BATCH = 8;
+
+__global__ __launch_bounds__(ROI_THREADS) void roi_pool_bwd_map_kernel(
+    const float* __restrict__ dout, const float* __restrict__ xs, const float* __restrict__ ys, float* __restrict__ dmap,
+    int B, int N, int P, int h, int w)
+{
+    __shared__ float part[ROI_THREADS / 64][ROI_C];
+    __shared__ int touched[ROI_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long pix = blockIdx.x;                                   // grid = B*h*w exactly: one pixel per workgroup
+    const int x = (int)(pix % w);
+    const int y = (int)((pix / w) % h);
+    const int b = (int)(pix / ((long)w * h));
+    float acc = 0.0f;
+    int any = 0;
+    for (int k0 = 0; k0 < P; k0 += 64) {
+        bool row_hit = false;
+        if (k0 + lane < P) {
+            const int y0 = corners_of(0.5f, ys[k0 + lane], h, w).y0;      // y0 does not depend on x
+            row_hit = (y0 == y || y0 + 1 == y);
+        }
+        unsigned long long kmask = __ballot(row_hit);
+        while (kmask) {
+            const int k = k0 + __builtin_ctzll(kmask);
+            kmask &= kmask - 1;
+            const float yk = ys[k];
+            for (int n0 = wave * 64; n0 < N; n0 += ROI_THREADS) {
+                bool hit = false;
+                float wgt = 0.0f;
+                if (n0 + lane < N) {
+                    const float xn = xs[((long)b * N + n0 + lane) * P + (P - 1 - k)];
+                    if (isfinite(xn)) {
+                        const Corners c = corners_of(xn, yk, h, w);
+                        if (c.x0 == x || c.x0 + 1 == x) {
+                            hit = true;
+                            wgt = (c.y0 == y) ? (c.x0 == x ? c.nw : c.ne) : (c.x0 == x ? c.sw : c.se);
+                        }
+                    }
+                }
+                unsigned long long nmask = __ballot(hit);
+                any |= nmask != 0ull;
+                while (nmask) {
+                    int js[ROI_BATCH];
+                    float gv[ROI_BATCH];
+#pragma unroll
+                    for (int t = 0; t < ROI_BATCH; ++t) {
+                        js[t] = -1;
+                        if (nmask) {
+                            js[t] = __builtin_ctzll(nmask);
+                            nmask &= nmask - 1;
+                        }
+                    }
+#pragma unroll
+                    for (int t = 0; t < ROI_BATCH; ++t)
+                        gv[t] = js[t] >= 0 ? dout[(((long)b * N + n0 + js[t]) * P + k) * ROI_C + lane] : 0.0f;
+#pragma unroll
+                    for (int t = 0; t < ROI_BATCH; ++t)
+                        if (js[t] >= 0) acc += gv[t] * __shfl(wgt, js[t]);
+                }
+            }
+        }
+    }
+    part[wave][lane] = acc;
+    if (lane == 0) touched[wave] = any;
+    __syncthreads();
+    if (wave == 0 && (touched[0] | touched[1] | touched[2] | touched[3])) {
+        const float s = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+        const size_t o = (((size_t)b * h + y) * w + x) * ROI_C + lane;
+        dmap[o] = dmap[o] + s;
     }
 }
 
@@ -186,8 +256,9 @@ PHNET_API int phnet_roi_pool_fwd(const float* fmap, const float* xs, const float
     return phnet_launch_status();
 }
 
-// dmap [B][h][w][64] is ACCUMULATED into (float atomics; caller zero-fills or passes an existing
-// gradient buffer; may be NULL); dxs [B][N][P] is overwritten (may be NULL when the anchors are detached).
+// dmap [B][h][w][64] is ACCUMULATED into (one add per pixel of a sum in a fixed order: bit-reproducible; caller
+// zero-fills or passes an existing gradient buffer; may be NULL); dxs [B][N][P] is overwritten (may be NULL when the
+// anchors are detached).
 PHNET_API int phnet_roi_pool_bwd(const float* dout, const float* fmap, const float* xs, const float* ys,
                                  float* dmap, float* dxs,
                                  int32_t B, int32_t N, int32_t P, int32_t h, int32_t w, int32_t C, void* stream)
@@ -196,8 +267,19 @@ PHNET_API int phnet_roi_pool_bwd(const float* dout, const float* fmap, const flo
     const long total = (long)B * N * P;
     if (total == 0 || (!dmap && !dxs)) return PHNET_OK;
     if (!dout || !fmap || !xs || !ys) return PHNET_ERR_ARG;
-    const unsigned blocks = (unsigned)ceil_div64(total, ROI_THREADS / 64);
-    hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(blocks), dim3(ROI_THREADS), 0, (hipStream_t)stream,
-                       dout, fmap, xs, ys, dmap, dxs, B, N, P, h, w);
-    return phnet_launch_status();
+    if (dmap) {
+        const long pixels = (long)B * h * w;
+        if (pixels > 0x7fffffffL) return PHNET_ERR_ARG;
+        hipLaunchKernelGGL(roi_pool_bwd_map_kernel, dim3((unsigned)pixels), dim3(ROI_THREADS), 0, (hipStream_t)stream,
+                           dout, xs, ys, dmap, B, N, P, h, w);
+        const int st = phnet_launch_status();
+        if (st != PHNET_OK) return st;
+    }
+    if (dxs) {
+        const unsigned blocks = (unsigned)ceil_div64(total, ROI_THREADS / 64);
+        hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(blocks), dim3(ROI_THREADS), 0, (hipStream_t)stream,
+                           dout, fmap, xs, ys, dxs, B, N, P, h, w);
+        return phnet_launch_status();
+    }
+    return PHNET_OK;
 }

@@ -36,7 +36,7 @@ import torch.nn as nn
 
 from oracle import lane_nms as oracle_nms
 from oracle import phnet_cpu as O
-from tests import synth
+from tests import fixtures, synth
 
 REF = "/root/reference"
 
@@ -380,7 +380,7 @@ def main():
     run_eval(model, g, 5, "eval", out)
     for k in ("train_fir", "train_sec", "eval_lines"):
         out[k] = out[k].astype(np.float32)
-    np.savez_compressed(os.path.join(HERE, "config2_r34_320x800.npz"), **out)
+    fixtures.save(os.path.join(HERE, "config2_r34_320x800.npz"), out)              # parts below 1 MiB (tests/fixtures.py)
     json.dump(names, open(os.path.join(HERE, "grad_names_resnet34.json"), "w"))
     json.dump(keys, open(os.path.join(HERE, "state_keys.json"), "w"))
     print("config2", out["train_loss"], out["eval_keep"].tolist())

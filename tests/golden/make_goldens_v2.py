@@ -33,7 +33,7 @@ import torch.nn as nn
 
 import make_goldens as MG
 from oracle import phnet_cpu_v2 as O2
-from tests import synth
+from tests import fixtures, synth
 
 
 def install_v2_shims():
@@ -168,7 +168,7 @@ def main():
     model, keys = build_reference(g)
     out = {}
     run_eval(model, g, 8, out, keep_fpn=True)
-    np.savez_compressed(os.path.join(HERE, "v2_tiny_r18_64x160.npz"), **out)
+    fixtures.save(os.path.join(HERE, "v2_tiny_r18_64x160.npz"), out)              # parts below 1 MiB (tests/fixtures.py)
     json.dump(keys, open(os.path.join(HERE, "state_keys_v2.json"), "w"))
     print("v2 tiny", out["keep"].tolist(), out["mem_rows"].tolist(),
           "hard-routed to branch B:", [(out["gate"][t].mean(0) >= 0.5).sum() for t in range(8)])
@@ -177,7 +177,7 @@ def main():
     model, _ = build_reference(g)
     out = {}
     run_eval(model, g, 6, out)
-    np.savez_compressed(os.path.join(HERE, "v2_r18_320x800.npz"), **out)
+    fixtures.save(os.path.join(HERE, "v2_r18_320x800.npz"), out)              # parts below 1 MiB (tests/fixtures.py)
     print("v2 320x800", out["keep"].tolist(), "hard-routed to branch B:", [(out["gate"][t].mean(0) >= 0.5).sum() for t in range(6)])
 
 

@@ -114,6 +114,13 @@ def test_roi_pool_fwd_bwd_vs_grid_sample(ops, h, w):
     dxs = ops.roi_pool_bwd(dev(gout.float()), nhwc(fmap.detach().float()), dev(xs.detach().float()), dev(ys.float()), dmap, True)
     close(dmap, fmap.grad.permute(0, 2, 3, 1), 1e-4)
     close(dxs, xs.grad, 1e-4)
+    # dmap is accumulated into, and bit-for-bit the same on every call (a fixed summation order, no float atomics)
+    base = torch.randn(B, h, w, C, device="cuda")
+    again = [base.clone(), base.clone()]
+    for d in again:
+        ops.roi_pool_bwd(dev(gout.float()), nhwc(fmap.detach().float()), dev(xs.detach().float()), dev(ys.float()), d, False)
+    assert torch.equal(again[0], again[1])
+    close(again[0] - base, fmap.grad.permute(0, 2, 3, 1), 1e-4)
 
 
 # ------------------------------------------------------------------------------------------------ conv / linear

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import synth
+from tests import fixtures, synth
 from oracle import phnet_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +27,7 @@ CASCADE_FRAC = 0.99      # share of chained-stage elements that must be within A
 
 
 def _gold(name):
-    return dict(np.load(os.path.join(GOLD, name)))
+    return fixtures.load(name)
 
 
 def _build(g: O.Geometry):

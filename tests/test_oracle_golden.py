@@ -9,7 +9,7 @@ import torch
 
 from oracle import lane_nms as ONMS
 from oracle import phnet_cpu as O
-from tests import synth
+from tests import fixtures, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -28,7 +28,7 @@ def _lines_close(a, b, what=""):
 
 
 def _load(name):
-    return dict(np.load(os.path.join(GOLD, name)))
+    return fixtures.load(name)
 
 
 def _train(g, T, counts=None):

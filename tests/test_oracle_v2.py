@@ -9,14 +9,14 @@ import torch
 
 from oracle import lane_nms as ONMS
 from oracle import phnet_cpu_v2 as O2
-from tests import synth
+from tests import fixtures, synth
 from tests.test_oracle_golden import _lines_close
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _load(name):
-    return dict(np.load(os.path.join(GOLD, name)))
+    return fixtures.load(name)
 
 
 def _check(gold, g, T, fpn=False):

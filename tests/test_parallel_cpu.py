@@ -232,3 +232,26 @@ def test_bench_gpus_n_launches_n_ranks():
     bad = subprocess.run([sys.executable, bench, "--gpus", "2", "--rendezvous-only"], env=dict(env, WORLD_SIZE="3", RANK="0"),
                          capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE=3" in (bad.stderr + bad.stdout)
+
+
+def test_bench_dump_outputs_are_bounded_seeded_and_layout_free(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss / params / grads / buffers as float32 .npy, each array at most DUMP_SAMPLE elements, the same
+    sampled positions on every call, and tensors taken in their logical element order (a channels_last copy of the model dumps
+    the same arrays)."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 50)
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.BatchNorm2d(8))
+    loss = m(torch.randn(2, 3, 8, 8)).square().mean()
+    loss.backward()
+    bench.dump_outputs(str(tmp_path / "a"), m, loss)
+    bench.dump_outputs(str(tmp_path / "b"), m.to(memory_format=torch.channels_last), loss)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["buffers.npy", "grads.npy", "loss.npy", "params.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and 0 < a.size <= 50, (n, a.dtype, a.size)
+        assert np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == np.float32(loss.item())
+    assert np.load(tmp_path / "a" / "buffers.npy").size == 16                    # BatchNorm running mean + var: below the cap, whole

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 from oracle import lane_nms as ONMS
 from oracle import phnet_cpu as O
 from oracle import phnet_cpu_v2 as O2
-from tests import synth
+from tests import fixtures, synth
 from tests.test_model_gpu import ACT_TOL, _close, _close_lines
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +23,7 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _gold(name):
-    return dict(np.load(os.path.join(GOLD, name)))
+    return fixtures.load(name)
 
 
 def _build(g: O2.GeometryV2):
