@@ -351,6 +351,27 @@ int phnet_gate_tail_bwd(const float* dout, const float* out, const float* h, con
 int phnet_blend_priors(const float* gate, const float* a, const float* b, const int64_t* idx, float* priors, float* on_map,
                        int32_t N, int32_t W, int32_t P, void* stream);
 
+/* ---- streaming inference: the cross-frame memory of B live video streams as a device-resident token ring (csrc/stream.hip;
+ * replaces the host-side FIFO of Router4OL.py:555-556 and its per-frame torch.cat, so that ONE captured hipGraph serves every
+ * frame of a video).  State, caller-allocated: ring [S][B][W][L+1][E], ring_valid u8 [S][B][W][L+1] (S stages, B streams,
+ * W = save_freq_max slots, L = max_lanes);  n i32[B] = frames pushed since the stream's last reset (reset = the caller writes
+ * n[b] = 0, stream-ordered; the ring need not be cleared);  cursor i32[B] = scratch word that carries n from window to push.
+ * Per frame: window, (the frame's forward), push - no launch reads the word it advances.
+ * phnet_stream_window: the memory the frame attends to, oldest remembered frame first, empty slots LAST (zero rows, marked
+ *   invalid): window [S][B][W*(L+1)][E], window_valid u8 [S][B][W*(L+1)], has_memory u8[B] = n[b] > 0.  With c = min(n, W),
+ *   logical slot j < c is physical slot (n - c + j) % W.  Also publishes cursor[b] = n[b].  E % 4 == 0.
+ * phnet_stream_push: the memory entry of this frame for every stage and stream - phnet_memory_tokens of feat [S][B][N][E] and
+ *   anchors_sorted i64[B][L] (-1 padded), bit-identical to it - written to physical slot cursor[b] % W; then n[b] = cursor[b] + 1.
+ *   1 <= L < N, E <= 1024.
+ * phnet_stream_select: feat[b] = attn[b] (both [B][N][E]) where has_memory[b] == 0, in place: the cross-frame decoder always
+ *   runs in a captured step, and the streams without a memory take its input instead (Router4OL.py:349-353).  E % 4 == 0. ---- */
+int phnet_stream_window(const float* ring, const uint8_t* ring_valid, const int32_t* n, int32_t* cursor, float* window,
+                        uint8_t* window_valid, uint8_t* has_memory, int32_t S, int32_t B, int32_t W, int32_t E, int32_t L,
+                        void* stream);
+int phnet_stream_push(const float* feat, const int64_t* anchors_sorted, float* ring, uint8_t* ring_valid, const int32_t* cursor,
+                      int32_t* n, int32_t S, int32_t B, int32_t W, int32_t N, int32_t E, int32_t L, void* stream);
+int phnet_stream_select(const float* attn, const uint8_t* has_memory, float* feat, int32_t B, int32_t N, int32_t E, void* stream);
+
 /* ---- Router4OLV2 model family (what testOLV3.py imports; inference only - its training path cannot run as shipped) ----
  * phnet_gate_v2_fwd: AdaptiveRouter4LaneV2.forward (libs/models/Router.py:83-132) in one launch: Conv1d(k3, pad 1, no bias)
  *   + BatchNorm1d + ReLU, Conv1d(k1) + BatchNorm1d + ReLU, Flatten, Linear(C2*P -> P), mean over the P outputs, sigmoid.

@@ -837,6 +837,60 @@ def memory_tokens(feat, rows, out=None):
     return tokens, valid
 
 
+def _stream_dims(ring, ring_valid, n, cursor):
+    """(S, B, W, L, E) of a token ring [S,B,W,L+1,E] after checking the state tensors that go with it."""
+    _req(ring, name="ring"); _req(n, torch.int32, "n"); _req(cursor, torch.int32, "cursor")
+    if ring.dim() != 5:
+        raise ValueError("stream: ring must be [S,B,W,L+1,E]")
+    s, b, w, l1, e = ring.shape
+    if (ring_valid.dtype != torch.bool or not ring_valid.is_contiguous() or tuple(ring_valid.shape) != (s, b, w, l1)
+            or n.numel() != b or cursor.numel() != b or l1 < 2):
+        raise ValueError("stream: ring_valid must be bool [S,B,W,L+1] (contiguous), n and cursor int32 [B], L >= 1")
+    return s, b, w, l1 - 1, e
+
+
+def stream_window(ring, ring_valid, n, cursor, out=None):
+    """The memory the next frame of every stream attends to, in logical order (oldest first, empty slots last and invalid):
+    (window [S,B,W*(L+1),E], window_valid bool [S,B,W*(L+1)], has_memory bool [B]).  Publishes cursor = n.  One launch."""
+    s, b, w, l, e = _stream_dims(ring, ring_valid, n, cursor)
+    m = w * (l + 1)
+    if out is not None:
+        window, valid, has = out
+        _req(window, name="window out")
+        if (tuple(window.shape) != (s, b, m, e) or valid.dtype != torch.bool or has.dtype != torch.bool or not valid.is_contiguous()
+                or not has.is_contiguous() or tuple(valid.shape) != (s, b, m) or has.numel() != b):
+            raise ValueError("stream_window: out = (window [S,B,W*(L+1),E] f32, window_valid bool [S,B,W*(L+1)], has_memory bool [B])")
+    else:
+        window = torch.empty((s, b, m, e), dtype=torch.float32, device=ring.device)
+        valid = torch.empty((s, b, m), dtype=torch.bool, device=ring.device)
+        has = torch.empty((b,), dtype=torch.bool, device=ring.device)
+    check(lib().phnet_stream_window(_ptr(ring), _ptr(ring_valid), _ptr(n), _ptr(cursor), _ptr(window), _ptr(valid), _ptr(has),
+                                    s, b, w, e, l, _stream()), "phnet_stream_window")
+    return window, valid, has
+
+
+def stream_push(feat, anchors_sorted, ring, ring_valid, n, cursor):
+    """feat [S,B,N,E] and anchors_sorted i64[B,L] (-1 padded) -> the memory entry of this frame (memory_tokens of every stage and
+    stream) in ring slot cursor % W, then n = cursor + 1.  One launch; needs a stream_window since the last push."""
+    s, b, w, l, e = _stream_dims(ring, ring_valid, n, cursor)
+    _req(feat, name="feat"); _req(anchors_sorted, torch.int64, "anchors_sorted")
+    if feat.dim() != 4 or feat.shape[0] != s or feat.shape[1] != b or feat.shape[3] != e or tuple(anchors_sorted.shape) != (b, l):
+        raise ValueError(f"stream_push: feat {tuple(feat.shape)} / anchors {tuple(anchors_sorted.shape)} vs ring {tuple(ring.shape)}")
+    check(lib().phnet_stream_push(_ptr(feat), _ptr(anchors_sorted), _ptr(ring), _ptr(ring_valid), _ptr(cursor), _ptr(n),
+                                  s, b, w, feat.shape[2], e, l, _stream()), "phnet_stream_push")
+
+
+def stream_select(attn, has_memory, feat):
+    """feat[b] = attn[b] (both [B,N,E]) for the streams with has_memory[b] == False, in place; returns feat.  One launch."""
+    _req(attn, name="attn"); _req(feat, name="feat")
+    if attn.dim() != 3 or attn.shape != feat.shape or has_memory.dtype != torch.bool or has_memory.numel() != attn.shape[0] \
+            or not has_memory.is_contiguous() or has_memory.device != attn.device:
+        raise ValueError("stream_select: attn / feat [B,N,E] f32 and has_memory bool [B] expected")
+    check(lib().phnet_stream_select(_ptr(attn), _ptr(has_memory), _ptr(feat), attn.shape[0], attn.shape[1], attn.shape[2], _stream()),
+          "phnet_stream_select")
+    return feat
+
+
 def gate_tail_fwd(h, w, b):
     _req(h, name="h"); _req(w, name="w"); _req(b, name="b")
     n, k = h.shape

@@ -281,10 +281,14 @@ class DetNetV2(nn.Module):
                                                 r["lines_b"].detach().contiguous(), self.sample_x_indexs)
         return {"predictions_fir": out_a, "predictions_sec": out_b}, attn_feats, gates
 
-    def forward_clips(self, x, last_cuts=None, stage0=None):
+    def forward_clips(self, x, last_cuts=None, stage0=None, stream=None):
         """Eval-time twin of forward() for the SAME frame index of B independent clips: x = (P3, P4, P5) [B,h,w,C];
         last_cuts = list over remembered frames of per-stage (tokens [B,L+1,E], valid [B,L+1]); stage0 = stage_front results
         [B,...] of stage 0.  Every head kernel sees B*N rows; attention and the memory tokens stay inside each clip.
+        stream (phnet_amd.stream.StreamState, instead of last_cuts): B live streams whose memory is the device-resident token
+        ring - every stage attends to stream.window[stage] (fixed size, empty slots masked), the decoder ALWAYS runs and the
+        streams whose memory is empty take its input back (hip_ops.stream_select), and the attn feats are written into
+        stream.feat[stage] for the push that follows the decode.
         Returns ({"predictions_fir": [...], "predictions_sec": [...]} with [B,N,6+S] entries, attn feats [B,N,2C], gates [B,N,1])."""
         levels = list(x)[::-1]
         last_cuts = last_cuts or []
@@ -298,8 +302,14 @@ class DetNetV2(nn.Module):
         for stage in range(self.refine_layers):
             front = stage0 if (stage == 0 and stage0 is not None) else self.stage_front(levels[stage], stage, priors, on_map, pro_feat)
             local = front["local"]
-            attn = torch.cat([local, pos], dim=-1)                                   # [B,N,2C]
-            if len(last_cuts):
+            # [B,N,2C]; a stream's copy lands where stream_push reads it
+            attn = torch.cat([local, pos], dim=-1) if stream is None else torch.cat([local, pos], dim=-1, out=stream.feat[stage])
+            if stream is not None:
+                mem, valid = stream.window[stage], stream.window_valid[stage]        # [B,W*(L+1),2C], [B,W*(L+1)]
+                feat = self.transformer_Dec(tgt=attn.reshape(B * N, -1), memory=mem.reshape(-1, mem.shape[-1]),
+                                            memory_key_valid=valid.reshape(-1), batch=B)
+                feat = K.stream_select(attn, stream.has_memory, feat.reshape(B, N, -1))
+            elif len(last_cuts):
                 mem = torch.cat([fr[stage][0] for fr in last_cuts], dim=1)           # [B,M,2C]
                 valid = torch.cat([fr[stage][1] for fr in last_cuts], dim=1)         # [B,M]
                 feat = self.transformer_Dec(tgt=attn.reshape(B * N, -1), memory=mem.reshape(-1, mem.shape[-1]),
@@ -763,6 +773,12 @@ class RouterOL(nn.Module):
         """One device->host copy per clip, then the host-side Lane construction (Router4OL.py:394-435)."""
         rows, n = kept_rows.cpu(), nums.cpu().tolist()
         return {"lane_lines": [self.detNet.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
+
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None):
+        """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
+        (phnet_amd.stream.LaneStream: reset / step / lanes); one captured hipGraph serves every frame."""
+        from phnet_amd.stream import LaneStream
+        return LaneStream(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw)
 
     def forward(self, inputs: dict):
         frame, lanes = inputs.values()

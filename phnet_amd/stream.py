@@ -1,0 +1,160 @@
+"""Streaming inference: one frame in, the lanes of that frame out, for B live video streams at once.
+
+PHNet is an online detector - the only thing carried from frame to frame is the cross-frame memory (the tokens of the kept lanes
+of the last `save_freq_max` frames).  `LaneStream` keeps that memory ON THE DEVICE as a token ring whose position is a word in
+GPU memory (csrc/stream.hip), so that ONE captured hipGraph serves every frame of a video of any length: the first frames after
+a reset, the frames after the ring has wrapped, one camera or several.  Per frame, on top of the T = 1 body of
+`RouterOL.infer_clips_device`: one `stream_window` launch (the memory of all stages in logical order), one `stream_select` per
+stage (streams without memory skip the cross-frame decoder, Router4OL.py:349-353) and one `stream_push` (the memory entry of
+this frame for all stages); no `memory_tokens`, no `torch.cat` of the memory, no host round trip.
+
+    s = model.open_stream(streams=B, frame_hw=(H, W))        # or LaneStream(model, streams=B, frame_hw=(H, W))
+    s.reset()                                                # all streams; s.reset(mask) bool[B]: only those (a camera cut)
+    rows, num, anchors = s.step(frames)                      # frames f32 [B,3,H,W]; device tensors, no host synchronisation
+    lanes = s.lanes(rows, num)                               # list over streams of Lane lists
+"""
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import hip_ops as K
+
+
+def window_order(n: int, W: int) -> List[int]:
+    """Physical ring slots of the frames a stream remembers after n pushes since its reset, oldest first: with c = min(n, W),
+    logical slot j < c is physical slot (n - c + j) % W (frame i was pushed to slot i % W).  The W - c empty slots are not listed:
+    `stream_window` puts them LAST, masked - the attention kernel deals its keys round-robin to the lanes of a row and skips
+    masked ones, so valid keys at unchanged positions followed by masked ones give the bits of the clip path's growing cat."""
+    if n < 0 or W < 1:
+        raise ValueError("window_order: n >= 0 and W >= 1")
+    c = min(n, W)
+    return [(n - c + j) % W for j in range(c)]
+
+
+class StreamState:
+    """Device state of B streams, allocated once: ring [S,B,W,L+1,E] / ring_valid bool [S,B,W,L+1] (the token ring; frame i of a
+    stream lives in slot i % W), n int32 [B] (frames pushed since the stream's reset) and cursor int32 [B] (the copy of n that
+    `stream_window` hands to `stream_push`: no launch reads the word it advances); plus the per-frame buffers window
+    [S,B,W*(L+1),E], window_valid bool [S,B,W*(L+1)], has_memory bool [B] and feat [S,B,N,E] (this frame's attn feats)."""
+
+    def __init__(self, stages: int, streams: int, slots: int, max_lanes: int, num_priors: int, width: int, device):
+        S, B, W, L, N, E = stages, streams, slots, max_lanes, num_priors, width
+        if min(S, B, W, L, N, E) < 1 or L >= N:
+            raise ValueError("StreamState: positive sizes and max_lanes < num_priors expected")
+        f32 = dict(dtype=torch.float32, device=device)
+        self.ring = torch.zeros((S, B, W, L + 1, E), **f32)
+        self.ring_valid = torch.zeros((S, B, W, L + 1), dtype=torch.bool, device=device)
+        self.n = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.cursor = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.window = torch.zeros((S, B, W * (L + 1), E), **f32)
+        self.window_valid = torch.zeros((S, B, W * (L + 1)), dtype=torch.bool, device=device)
+        self.has_memory = torch.zeros((B,), dtype=torch.bool, device=device)
+        self.feat = torch.zeros((S, B, N, E), **f32)
+
+    def load_window(self):
+        K.stream_window(self.ring, self.ring_valid, self.n, self.cursor, out=(self.window, self.window_valid, self.has_memory))
+
+    def push(self, anchors_sorted: torch.Tensor):
+        K.stream_push(self.feat, anchors_sorted.contiguous(), self.ring, self.ring_valid, self.n, self.cursor)
+
+    def reset(self, mask: Optional[torch.Tensor] = None):
+        """n[b] = 0 for the chosen streams, in stream order.  Validity follows from n, so the ring is not cleared."""
+        if mask is None:
+            self.n.zero_()
+        else:
+            self.n.masked_fill_(mask, 0)
+
+
+class LaneStream:
+    """model: a RouterOL (eval).  streams: B.  frame_hw: (H, W) of the network input.  graph=True: the step is captured once
+    (warmed up and captured the way GraphedInference does it) and replayed for every frame - a reset never recaptures;
+    graph=False runs the same launches eagerly.  reset_every=k resets all streams before frames 0, k, 2k, ... (k = 16 is the
+    chunking of the reference's testOL.py:104-117).  raw: a ClipPreprocessor - `step` then takes camera-format uint8 frames
+    [B,src_h,src_w,3] and the crop / resize / normalise launch is part of the step (and of the captured graph).
+
+    With graph=True the returned tensors are the graph's static outputs: the next `step` overwrites them."""
+
+    def __init__(self, model, streams: int = 1, frame_hw: Tuple[int, int] = None, graph: bool = True, reset_every: Optional[int] = None,
+                 raw=None, warmup: int = 2):
+        if reset_every is not None and reset_every < 1:
+            raise ValueError("reset_every must be a positive number of frames")
+        det = model.detNet
+        if frame_hw is None:
+            frame_hw = (det.img_h, det.img_w)
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("LaneStream: the model must be on the GPU; phnet_amd has no CPU path")
+        self.model, self.streams, self.reset_every, self.raw = model.eval(), int(streams), reset_every, raw
+        self.state = StreamState(det.refine_layers, self.streams, model.save_freq_max, det.cfg.max_lanes, det.num_priors,
+                                 det.transformer_Dec.layers[0].self_attn.embed_dim, dev)
+        if raw is not None:
+            if (raw.out_h, raw.out_w) != tuple(frame_hw):
+                raise ValueError(f"raw= resizes to {raw.out_h}x{raw.out_w}, frame_hw is {tuple(frame_hw)}")
+            self.frames = torch.zeros((self.streams, raw.src_h, raw.src_w, 3), dtype=torch.uint8, device=dev)
+        else:
+            self.frames = torch.zeros((self.streams, 3, *frame_hw), dtype=torch.float32, device=dev)
+        self.frame_index = 0                                      # host-side count of steps, for reset_every only
+        self.graph, self.out = None, None
+        if graph:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    self._body(self.frames)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.out = self._body(self.frames)
+            torch.cuda.synchronize()
+        self.reset()                                              # the warm-up frames are forgotten
+
+    @torch.no_grad()
+    def _body(self, frames: torch.Tensor):
+        """infer_clips_device's loop body for T = 1 on the B streams, the memory taken from / pushed to the device ring."""
+        model, det, st = self.model, self.model.detNet, self.state
+        B = self.streams
+        model._begin_clip()
+        x = frames if self.raw is None else self.raw(frames)
+        feats = model.backbone(x)
+        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(B, -1, -1),
+                                 det.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                 det.pro_embedding.weight.unsqueeze(0).expand(B, -1, -1))
+        st.load_window()
+        outputs, _, gates = det.forward_clips(feats, None, front0, stream=st)
+        d = torch.stack(gates, dim=0).mean(dim=0)
+        lines = outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
+        dec = det.decode_device(lines)
+        st.push(dec["anchors_sorted"])
+        model._begin_clip()
+        return dec["kept_rows"], dec["num"], dec["anchors"]
+
+    def reset(self, mask=None):
+        """Forget the memory of all streams, or of those where mask (bool [B]: tensor or sequence) is set - a camera cut.  The next
+        frame of a reset stream is decoded like the first frame of a clip.  Stream-ordered, outside the graph: never recaptures."""
+        if mask is not None and not torch.is_tensor(mask):
+            mask = torch.tensor(list(mask), dtype=torch.bool)
+        if mask is not None:
+            if mask.dtype != torch.bool or mask.numel() != self.streams:
+                raise ValueError(f"reset: bool mask of {self.streams} streams expected")
+            mask = mask.reshape(-1).to(self.state.n.device, non_blocking=True)
+        self.state.reset(mask)
+
+    def step(self, frames: torch.Tensor):
+        """One frame of every stream: frames f32 [B,3,H,W] (u8 [B,src_h,src_w,3] with raw=) on the device ->
+        (kept_rows [B,max_lanes,6+S], num [B], anchors [B,max_lanes]) on the device.  No host synchronisation."""
+        if frames.shape != self.frames.shape or frames.dtype != self.frames.dtype or not frames.is_cuda:
+            raise ValueError(f"step: {self.frames.dtype} device frames {tuple(self.frames.shape)} expected, "
+                             f"got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+        if self.reset_every is not None and self.frame_index % self.reset_every == 0:
+            self.state.reset()
+        self.frame_index += 1
+        if self.graph is None:
+            return self._body(frames.contiguous())
+        self.frames.copy_(frames, non_blocking=True)
+        self.graph.replay()
+        return self.out
+
+    def lanes(self, kept_rows: torch.Tensor, num: torch.Tensor) -> Sequence[list]:
+        """Device -> host copy of one step's result, then the host-side Lane construction: a list over streams of Lane lists."""
+        return self.model.lanes_from_device(kept_rows, num)["lane_lines"]
