@@ -11,7 +11,9 @@
  *   - return value: 0 = enqueued, <0 = error (no work enqueued unless stated):
  *       PHNET_ERR_ARG (-1) bad shape / null pointer / unsupported size,
  *       PHNET_ERR_WORKSPACE (-2) workspace too small, PHNET_ERR_LAUNCH (-3) HIP launch error;
- *   - re-entrant and thread-safe (no global state).
+ *   - re-entrant, with one exception: the conv / Linear / gate / dynamic-head entries read the process-global tuning struct
+ *     (kernel A/B switches; defaults = the product path).  Only include/phnet_hip_tuning.h writes it, and it must not change
+ *     while a step is being captured into a hipGraph.
  * Activation layout is NHWC; convolution weights are OHWI ([Co][R][S][Ci]) = the memory order of a
  * torch.channels_last OIHW parameter, so reference checkpoints load without a re-layout pass.
  */
@@ -95,15 +97,22 @@ int phnet_conv3p_pack(const float* w, void* packed, int32_t Co, int32_t Ci, int3
  * int64 first} sorted by `first` = running sum of the jobs' item counts 9*(Ca/16)*(Nn/32)*64; total = the sum of all counts */
 int phnet_conv3p_pack_jobs(const void* jobs, int32_t njobs, int64_t total, void* stream);
 uint64_t phnet_conv3p_stats_blocks(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes);
-int phnet_conv3p_splits(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes);
 int phnet_conv3p_fwd(const float* x, const void* packed, const float* bias, const float* addend, float* y, float* stats,
                      int32_t N, int32_t H, int32_t W, int32_t Ca, int32_t Nn, int32_t relu,
                      void* workspace, uint64_t ws_bytes, void* stream);
-/* host-side query (no device work; bm/bn/splits/k_tile are HOST pointers): tile, split-K factor and K-tile depth the
- * two calls above use, i.e. the template arguments of the conv_igemm_kernel<BM, BN, DGRAD, BKT, UNI> they launch
- * (UNI = uniform-tap variant: 64x64 tile and A-side channel count % BKT == 0). */
+/* host-side queries (no device work, callable without a GPU; HOST pointers), answered by the decision functions the launches
+ * call.  phnet_conv2d_plan: tile, split-K factor and K-tile depth of a forward GEMM of M x Co x K (M < 2^31).  phnet_*_kernel:
+ * the instantiation the launch entry of the same shape arguments runs, as rocprofv3 spells it after the namespace (e.g.
+ * "conv_igemm_kernel<64, 64, false, 16, true, 3, 4, true>"; name_cap bytes), and its split factor.  phnet_conv2d_kernel:
+ * dgrad = 0 names phnet_conv2d_fwd / _fwd_fused, 1 phnet_conv2d_dgrad; ws_bytes = 0 = no workspace. */
 int phnet_conv2d_plan(int64_t M, int32_t Co, int32_t K, uint64_t ws_bytes, int32_t* bm, int32_t* bn, int32_t* splits,
                       int32_t* k_tile);
+int phnet_conv2d_kernel(int32_t dgrad, int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S,
+                        int32_t stride, int32_t pad, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits);
+int phnet_conv2d_wgrad_kernel(int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S, int32_t stride,
+                              int32_t pad, int32_t has_dbias, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits);
+int phnet_linear_bwd_kernel(int32_t M, int32_t K, int32_t N, int32_t has_relu_mask, char* name, int32_t name_cap);
+int phnet_conv3p_kernel(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits);
 uint64_t phnet_conv2d_wgrad_workspace(int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co,
                                       int32_t R, int32_t S, int32_t stride, int32_t pad);
 /* dbias (optional, [Co]) = sum of dy over all pixels = the bias gradient, produced by the same launch. */

@@ -1,6 +1,6 @@
 /* Benchmark and A/B switches of libphnet_hip.so - NOT part of the drop-in boundary (include/phnet_hip.h).
  *
- * Process-global, not thread-safe, never called by the product path: tests/ and tests/tools/ use them to run one kernel
+ * Process-global (one struct, csrc/tuning.h), not thread-safe, never called by the product path: tests/ and tests/tools/ use them to run one kernel
  * against another on the same operands (e.g. the generic weight-gradient kernel against the three-taps one) and to sweep
  * tile / split-K plans.  Kept in a header of their own so that the public header documents only what a caller of the
  * reference's libs.models / libs.ops path needs. */
@@ -33,6 +33,8 @@ int phnet_tune_gate_wave(int32_t on);
  * apply; forward: one wavefront per anchor AND 16-row fragment, backward: four per anchor), 3 = the one-wavefront-per-anchor forms of both,
  * 0 = the LDS / FMA kernels of csrc/dynhead.hip */
 int phnet_tune_dyn_mfma(int32_t on);
+int phnet_tune_reset(void);     /* every switch above back to its default */
+int phnet_tune_mma_get(void);   /* the current phnet_tune_mma mode */
 
 #ifdef __cplusplus
 }

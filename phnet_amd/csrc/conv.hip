@@ -18,7 +18,9 @@
 //
 // Roofline: MFMA-bound (f32-input MFMA, 157.3 TF/s dense).  Algorithmic FLOPs = 2*M*N*K.
 #include <type_traits>
+#include <cstdio>
 #include "igemm.h"
+#include "tuning.h"
 #include "wgrad3s.h"
 static constexpr bool g_interleave = true;                   // MFMA / VALU interleave hints of the staged-split loops
 
@@ -455,7 +457,6 @@ __global__ __launch_bounds__(THREADS) void conv_igemm_kernel(
 // prefetch ring of one unit (three weight tiles + the next A block); epilogue (bias / addend / ReLU / BatchNorm statistics /
 // split-K partials) as in igemm_tile.  DGRAD: the same gather on dY with the flipped, transposed weight as B (K-strided planes).
 constexpr int T3_AROWS = 66;
-int g_taps3 = 1;                                             // tuning aid: phnet_tune_force_k_tile(-5 / -6) switches this kernel off / on
 template <bool DGRAD>
 __global__ __launch_bounds__(THREADS) void conv3x3s1_kernel(
     const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias,
@@ -996,10 +997,6 @@ __global__ __launch_bounds__(THREADS) void conv_wgrad_kernel(
 // outside the frame are staged as zeros (the pixel block may span image rows and frames: rows are tested one by one).
 // bf16x3 arithmetic, buffer loads; Ci, Co multiples of 64.
 constexpr int W3_THREADS = 768;
-int g_wgrad3 = 1, g_wgrad3_target = 256;                     // tuning aids (phnet_tune_wgrad: bit 3 of arg 0 switches it off; a negative
-int g_wgrad3_bkw = 16;                                       // second argument sets its workgroup target, bit 4 selects 32-pixel steps)
-int g_wgrad3s = 1;                                           // producer / consumer variant (csrc/wgrad3s.hip) where no bias gradient is asked for; bit 5 switches it off
-int g_wgrad1s = 1;                                           // 128 x 128 producer / consumer kernel for many-row Linear layers (csrc/wgrad1s.hip); bit 6 switches it off
 template <int BKW> struct Wgrad3Lds {
     static constexpr int ROWS = BKW + 2;                     // X rows of a step: pixels pt-1 .. pt+BKW of the shifted image row
     static constexpr int PITCH = KStridedPlanes<64, BK>::PITCH;      // 192 bytes: 64 bf16 + pad (igemm.h)
@@ -1388,18 +1385,14 @@ __global__ void pad_channels_kernel(const float* __restrict__ src, float* __rest
 
 struct TileChoice { int bm, bn; };
 
-int g_mma_mode = 3;                                          // 3 (default): exact 3-term bf16 split at staging; 0: f32-input MFMA; 1 / 2: bf16 splits in registers (phnet_tune_mma)
-int g_buf_loads = 1;                                         // buffer-load operand path where it applies (tuning: phnet_tune_force_k_tile(-200 / -201))
-int g_pf = 4;                                                // register prefetch depth in K tiles (tuning: phnet_tune_force_k_tile(-101 / -102 / -104))
-int g_deep_kt3 = 64;                                         // K tile of the few-rows GEMMs in mode 3 (tuning: phnet_tune_force_k_tile(-32 / -64))
-
 TileChoice pick_tile(long M, long N)
 {
     // Measured on MI355X (tests/tools/bench_conv.py): the problems of this path are small (a 5-frame clip), so what
     // matters is the number of co-resident workgroups per CU, not the tile's arithmetic intensity: 64x64 tiles with
     // the block count topped up to ~1250 by split-K beat the larger tiles on every trunk layer (72-80 us vs 85-130 us).
-    if (g_mma_mode == 3 && M <= 2048) return {64, 64};          // (64x64 is the fastest tile up to the 1200 rows of a batched clip)
-    if (g_mma_mode >= 1) {
+    const int mma = tuning().mma_mode;
+    if (mma == 3 && M <= 2048) return {64, 64};                 // (64x64 is the fastest tile up to the 1200 rows of a batched clip)
+    if (mma >= 1) {
         // split-bf16: the loop is bound by the operand split (VALU) and the LDS reads per MFMA, both of which shrink with
         // the wave tile - problems with enough tiles take the larger ones (bench_conv.py --mma --clips 8: 128x128 is
         // 15-20 % faster than 64x64 on the 8-clip trunk layers, and slower on every 1-clip layer)
@@ -1415,29 +1408,23 @@ struct ConvPlan { int bm, bn, splits; long tiles; };
 // (the MFMA work per barrier is 5x shorter there; measured 44-54 us vs 51-58 us on the trunk layers)
 int k_tile_for(long M, int K, int ci, int bm, int bn)
 {
+    const int mma = tuning().mma_mode;
     // few-rows GEMMs (one frame of the lane head: 240 rows): deep K tiles.  With the frames of a clip batched (1200 rows) the
     // trunk plan wins in the staged-split arithmetic: 1024 -> 8192 174 vs 260 us, 4608 -> 1024 96 vs 146 us (bench_conv --only clipB)
-    if (M <= (g_mma_mode == 3 ? 256 : 2048) && K >= 64) return (g_mma_mode == 3 && g_deep_kt3 == 32) ? 32 : 64;
-    if (g_mma_mode == 3) return BK;                                   // 37 KB of LDS per 64x64 workgroup: four per CU
-    if (g_mma_mode >= 1 && bm == 64 && bn == 64 && ci % 32 == 0) return 32;
+    if (M <= (mma == 3 ? 256 : 2048) && K >= 64) return (mma == 3 && tuning().deep_kt3 == 32) ? 32 : 64;
+    if (mma == 3) return BK;                                          // 37 KB of LDS per 64x64 workgroup: four per CU
+    if (mma >= 1 && bm == 64 && bn == 64 && ci % 32 == 0) return 32;
     return BK;
 }
 
-int g_force_bm = 0, g_force_bn = 0, g_force_splits = 0;      // tuning aid (phnet_tune_force_conv_tile)
-int g_force_kt = 0;                                          // tuning aid (phnet_tune_force_k_tile)
-int g_uniform_tap = 1;                                       // tuning aid (phnet_tune_force_k_tile(-1) switches the uniform-tap variant off)
-int g_wgrad_bm128 = 1, g_wgrad_target = 768;                // tuning aids (phnet_tune_wgrad)
-int g_wgrad_bkw = 16;                                        // tuning aid: pixels per K step of the staged-split wgrad kernel (phnet_tune_wgrad bit 2 of arg 0 -> 32)
-int g_wgrad_smallp = 1;                                      // bit 1 of phnet_tune_wgrad's first argument switches the few-rows kernel off
-int g_smallp_max_tiles = 400;                                 // measured: 64 -> 400 tiles saves 0.75 ms per step, 1300 nothing more
-
 ConvPlan plan_conv(long M, int Co, int K, bool has_ws, size_t ws_bytes)
 {
+    const Tuning& tn = tuning();
     TileChoice t = pick_tile(M, Co);
-    if (g_force_bm) {
-        t = {g_force_bm, g_force_bn};
+    if (tn.force_bm) {
+        t = {tn.force_bm, tn.force_bn};
         ConvPlan f{t.bm, t.bn, 1, ceil_div64(M, t.bm) * ceil_div64(Co, t.bn)};
-        int splits = g_force_splits > 0 ? g_force_splits : 1;
+        int splits = tn.force_splits > 0 ? tn.force_splits : 1;
         while (splits > 1 && (!has_ws || (size_t)splits * M * Co * sizeof(float) > ws_bytes)) --splits;
         f.splits = splits;
         return f;
@@ -1446,7 +1433,7 @@ ConvPlan plan_conv(long M, int Co, int K, bool has_ws, size_t ws_bytes)
     // split K until ~1250 workgroups are in flight (about 5 per CU), keeping >= 256 of K per split
     // K-tile-64 plans (M <= 2048: the head GEMMs) hold 70 KB of LDS per workgroup = 2 workgroups per CU, so ~512 tiles already
     // fill the chip in one round and a split only adds the reduce pass (hyper-net 1024 -> 8192 at 240 rows: 54 vs 62 us)
-    const bool deep = M <= (g_mma_mode == 3 ? 256 : 2048) && K >= 64;
+    const bool deep = M <= (tn.mma_mode == 3 ? 256 : 2048) && K >= 64;
     if (has_ws && p.tiles < (deep ? 400 : 900)) {
         int splits = (int)min((long)8, max((long)1, (1250 + p.tiles / 2) / p.tiles));
         while (splits > 1 && K / splits < 256) --splits;
@@ -1456,25 +1443,61 @@ ConvPlan plan_conv(long M, int Co, int K, bool has_ws, size_t ws_bytes)
     return p;
 }
 
+// What one forward / data-gradient call launches.  Decided once here; launch_conv launches it, conv_kernel_name spells it.
+struct ConvPick {
+    bool taps3;                          // conv3x3s1_kernel<dgrad>; else conv_igemm_kernel<bm, bn, dgrad, bkt, uni, mma, pf, buf>
+    bool dgrad, uni, buf;
+    int bm, bn, bkt, mma, pf, splits;
+    long tiles;
+};
+
+ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes)
+{
+    const Tuning& tn = tuning();
+    const long M = (long)g.N * g.Ho * g.Wo;
+    const int K = g.R * g.S * g.Ci;
+    const ConvPlan t = plan_conv(M, g.Co, K, has_ws, ws_bytes);
+    ConvPick p{};
+    p.dgrad = dgrad; p.bm = t.bm; p.bn = t.bn; p.splits = t.splits; p.tiles = t.tiles;
+    // deep K tiles for skinny (latency-bound) problems: few row tiles and K long enough to fill them
+    p.bkt = tn.force_kt ? tn.force_kt : k_tile_for(M, K, g.Ci, t.bm, t.bn);
+    p.mma = tn.mma_mode;
+    p.pf = p.mma == 3 ? ((tn.pf == 4 || tn.pf == 2) ? tn.pf : 1) : (p.mma == 0 && tn.pf == 4) ? 4 : 1;     // the instantiated ring depths
+    // uniform-tap variant (the production tile only): the A-side channel count is a multiple of the K tile
+    const bool uni = (g.Ci % p.bkt) == 0 && tn.uniform_tap;
+    p.uni = uni && t.bm == 64 && t.bn == 64;
+    p.buf = p.uni && g.in_dil == 1 && tn.buf_loads && p.mma == 3;
+    p.taps3 = tn.taps3 && p.buf && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Ho == g.Hi && g.Wo == g.Wi &&
+              p.bkt == 16 && p.pf == 4 && g.Wi >= 2 && M * (long)g.Ci * 4 < 0x7fffffffL && (long)g.Co * K * 4 < 0x7fffffffL;
+    return p;
+}
+
+// the instantiation launch_conv's switch below launches for a pick, as rocprofv3 spells it
+int conv_kernel_name(const ConvPick& p, char* name, int cap)
+{
+    static const char* const tf[2] = {"false", "true"};
+    const int n = p.taps3 ? snprintf(name, (size_t)cap, "conv3x3s1_kernel<%s>", tf[p.dgrad])
+                          : snprintf(name, (size_t)cap, "conv_igemm_kernel<%d, %d, %s, %d, %s, %d, %d, %s>", p.bm, p.bn, tf[p.dgrad], p.bkt,
+                                     tf[p.uni], p.mma, p.pf, tf[p.buf]);
+    return n < cap ? PHNET_OK : PHNET_ERR_ARG;
+}
+
 template <bool DGRAD>
 int launch_conv(const float* X, const float* W, const float* bias, const float* addend, float* out, float* workspace,
                 size_t ws_bytes, ConvShape g, int relu, hipStream_t st, float* stats = nullptr)
 {
+    const ConvPick p = pick_conv(g, DGRAD, workspace != nullptr, ws_bytes);
     const long M = (long)g.N * g.Ho * g.Wo;
     const int K = g.R * g.S * g.Ci;
-    const ConvPlan t = plan_conv(M, g.Co, K, workspace != nullptr, ws_bytes);
-    const long tiles = t.tiles;
-    const int splits = t.splits;
+    const int splits = p.splits;
     g.splits = splits;
     float* dst = splits > 1 ? workspace : out;
-    dim3 grid((unsigned)tiles, 1, (unsigned)splits);
-    // deep K tiles for skinny (latency-bound) problems: few row tiles and K long enough to fill them
-    const int bkt = g_force_kt ? g_force_kt : k_tile_for(M, K, g.Ci, t.bm, t.bn);
-    const int ksteps = (K + bkt - 1) / bkt;
-    g.k_per_split = ((ksteps + splits - 1) / splits) * bkt;
+    dim3 grid((unsigned)p.tiles, 1, (unsigned)splits);
+    const int ksteps = (K + p.bkt - 1) / p.bkt;
+    g.k_per_split = ((ksteps + splits - 1) / splits) * p.bkt;
 #define PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, MMA_, PF_)                                                           \
     do {                                                                                                                \
-        if (UNI_ && g.in_dil == 1 && g_buf_loads && MMA_ == 3) PHNET_LAUNCH_CONV____(BM_, BN_, BKT_, UNI_, MMA_, PF_, UNI_); \
+        if (p.buf) PHNET_LAUNCH_CONV____(BM_, BN_, BKT_, UNI_, MMA_, PF_, UNI_);                                        \
         else PHNET_LAUNCH_CONV____(BM_, BN_, BKT_, UNI_, MMA_, PF_, false);                                             \
     } while (0)
 #define PHNET_LAUNCH_CONV____(BM_, BN_, BKT_, UNI_, MMA_, PF_, BUF_)                                                    \
@@ -1496,39 +1519,33 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
 #define PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, MMA_) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, MMA_, 1)
 #define PHNET_LAUNCH_CONV_(BM_, BN_, BKT_, UNI_)                                                                        \
     do {                                                                                                                \
-        if (g_mma_mode == 1) PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, 1);                                              \
-        else if (g_mma_mode == 2) PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, 2);                                         \
-        else if (g_mma_mode == 3 && g_pf == 4) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 4);                        \
-        else if (g_mma_mode == 3 && g_pf == 2) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 2);                        \
-        else if (g_mma_mode == 3) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 1);                                     \
-        else if (g_pf == 4) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 0, 4);                                           \
+        if (p.mma == 1) PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, 1);                                                   \
+        else if (p.mma == 2) PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, 2);                                              \
+        else if (p.mma == 3 && p.pf == 4) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 4);                             \
+        else if (p.mma == 3 && p.pf == 2) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 2);                             \
+        else if (p.mma == 3) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 3, 1);                                          \
+        else if (p.pf == 4) PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, 0, 4);                                           \
         else PHNET_LAUNCH_CONV__(BM_, BN_, BKT_, UNI_, 0);                                                              \
     } while (0)
 #define PHNET_LAUNCH_CONV(BM_, BN_, UNI_)                                                                               \
     do {                                                                                                                \
-        if (bkt == 64) PHNET_LAUNCH_CONV_(BM_, BN_, 64, UNI_);                                                          \
-        else if (bkt == 32) PHNET_LAUNCH_CONV_(BM_, BN_, 32, UNI_);                                                     \
+        if (p.bkt == 64) PHNET_LAUNCH_CONV_(BM_, BN_, 64, UNI_);                                                        \
+        else if (p.bkt == 32) PHNET_LAUNCH_CONV_(BM_, BN_, 32, UNI_);                                                   \
         else PHNET_LAUNCH_CONV_(BM_, BN_, 16, UNI_);                                                                    \
     } while (0)
-    // uniform-tap variant (the production tile only): the A-side channel count is a multiple of the K tile
-    const bool uni = (g.Ci % bkt) == 0 && g_uniform_tap;
-    if (g_taps3 && uni && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.in_dil == 1 && g.Ho == g.Hi && g.Wo == g.Wi &&
-        t.bm == 64 && t.bn == 64 && bkt == 16 && g_mma_mode == 3 && g_buf_loads && g_pf == 4 && g.Wi >= 2 &&
-        M * (long)g.Ci * 4 < 0x7fffffffL && (long)g.Co * K * 4 < 0x7fffffffL) {
+    if (p.taps3) {
         const int units = 3 * (g.Ci / 16);
         g.k_per_split = (units + splits - 1) / splits;                   // in units for this kernel
         constexpr size_t lds_ = 2 * 3 * T3_AROWS * KContigPlanes<64, 16>::PITCH +
                                 2 * (size_t)(DGRAD ? KStridedPlanes<64, 16>::BYTES : KContigPlanes<64, 16>::BYTES) + 3 * 512;
         hipLaunchKernelGGL((conv3x3s1_kernel<DGRAD>), grid, dim3(THREADS), lds_, st,
                            X, W, bias, addend, dst, g, relu, splits > 1 ? (float*)nullptr : stats);
-    } else
-    {
-    if (t.bm == 128 && t.bn == 128) PHNET_LAUNCH_CONV(128, 128, false);
-    else if (t.bm == 128 && t.bn == 64) PHNET_LAUNCH_CONV(128, 64, false);
-    else if (t.bm == 64 && t.bn == 128) PHNET_LAUNCH_CONV(64, 128, false);
-    else if (uni) PHNET_LAUNCH_CONV(64, 64, true);
-    else PHNET_LAUNCH_CONV(64, 64, false);
     }
+    else if (p.bm == 128 && p.bn == 128) PHNET_LAUNCH_CONV(128, 128, false);
+    else if (p.bm == 128 && p.bn == 64) PHNET_LAUNCH_CONV(128, 64, false);
+    else if (p.bm == 64 && p.bn == 128) PHNET_LAUNCH_CONV(64, 128, false);
+    else if (p.uni) PHNET_LAUNCH_CONV(64, 64, true);
+    else PHNET_LAUNCH_CONV(64, 64, false);
 #undef PHNET_LAUNCH_CONV____
 #undef PHNET_LAUNCH_CONV___
 #undef PHNET_LAUNCH_CONV__
@@ -1542,62 +1559,64 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
     return phnet_launch_status();
 }
 
+bool conv_args_ok(int N, int Hi, int Wi, int Ci, int Co, int R, int S, int stride, int pad)
+{
+    return !(N < 0 || Hi < 1 || Wi < 1 || Ci < 4 || Co < 4 || (Ci & 3) || (Co & 3) || R < 1 || S < 1 || stride < 1 || pad < 0);
+}
+
+// GEMM view of the forward; false where the output image would be empty
+bool fwd_shape(int N, int Hi, int Wi, int Ci, int Co, int R, int S, int stride, int pad, ConvShape* g)
+{
+    *g = ConvShape{};
+    g->N = N; g->Hi = Hi; g->Wi = Wi; g->Ci = Ci; g->Co = Co; g->R = R; g->S = S;
+    g->Ho = (Hi + 2 * pad - R) / stride + 1;
+    g->Wo = (Wi + 2 * pad - S) / stride + 1;
+    g->stride = stride; g->pad = pad; g->in_dil = 1;
+    return g->Ho >= 1 && g->Wo >= 1;
+}
+
+// GEMM view of the data gradient (A side = dY, output = dX); false for paddings it does not support
+bool dgrad_shape(int N, int Hi, int Wi, int Ci, int Co, int R, int S, int stride, int pad, ConvShape* g)
+{
+    *g = ConvShape{};
+    g->N = N;
+    g->Hi = (Hi + 2 * pad - R) / stride + 1;      // A-side image = dY
+    g->Wi = (Wi + 2 * pad - S) / stride + 1;
+    g->Ci = Co;
+    g->Ho = Hi; g->Wo = Wi; g->Co = Ci;            // GEMM output = dX
+    g->R = R; g->S = S;
+    g->stride = 1; g->pad = R - 1 - pad; g->in_dil = stride;
+    if (R != S && (S - 1 - pad) != g->pad) return false;        // square padding only
+    return g->pad >= 0;
+}
+
 }  // namespace
 
-// Which kernel instantiation / split-K factor phnet_conv2d_fwd / _dgrad will use for a GEMM of M x Co x K
-// (profiling aid for bench.py: lets the host attribute event timings to one kernel symbol).
+// Which tile / split-K factor / K tile phnet_conv2d_fwd runs a GEMM of M x Co x K with (a 1x1 convolution of K channels over M
+// pixels; M < 2^31).  Answered by the pick_conv the launch itself calls.
 PHNET_API int phnet_conv2d_plan(int64_t M, int32_t Co, int32_t K, uint64_t ws_bytes, int32_t* bm, int32_t* bn, int32_t* splits,
                                 int32_t* k_tile)
 {
-    if (M < 1 || Co < 1 || K < 1 || !bm || !bn || !splits || !k_tile) return PHNET_ERR_ARG;
-    const ConvPlan p = plan_conv((long)M, Co, K, ws_bytes > 0, (size_t)ws_bytes);
-    *bm = p.bm; *bn = p.bn; *splits = p.splits;
-    *k_tile = g_force_kt ? g_force_kt : k_tile_for((long)M, K, K, p.bm, p.bn);   // (K stands in for the channel count)
+    ConvShape g;
+    if (M < 1 || M > 0x7fffffffL || Co < 1 || K < 1 || !bm || !bn || !splits || !k_tile) return PHNET_ERR_ARG;
+    fwd_shape((int)M, 1, 1, K, Co, 1, 1, 1, 0, &g);
+    const ConvPick p = pick_conv(g, false, ws_bytes > 0, (size_t)ws_bytes);
+    *bm = p.bm; *bn = p.bn; *splits = p.splits; *k_tile = p.bkt;
     return PHNET_OK;
 }
 
-// Tuning aid (process-global, not thread-safe, never used by the product path): force the tile (64|128 each) and
-// split-K factor of the next phnet_conv2d_fwd/_dgrad calls; bm = 0 restores the built-in heuristic.
-PHNET_API int phnet_tune_force_conv_tile(int32_t bm, int32_t bn, int32_t splits)
+// Host-only query: the kernel instantiation phnet_conv2d_fwd / _fwd_fused (dgrad = 0) or phnet_conv2d_dgrad (dgrad = 1) launches
+// for the same shape arguments, as rocprofv3 spells it, and its split-K factor.
+PHNET_API int phnet_conv2d_kernel(int32_t dgrad, int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S,
+                                  int32_t stride, int32_t pad, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits)
 {
-    if (bm != 0 && !((bm == 64 || bm == 128) && (bn == 64 || bn == 128))) return PHNET_ERR_ARG;
-    g_force_bm = bm; g_force_bn = bn; g_force_splits = splits;
-    return PHNET_OK;
-}
-
-PHNET_API int phnet_tune_wgrad(int32_t allow_bm128, int32_t target_blocks)
-{
-    if (target_blocks == 0 || target_blocks < -1024) return PHNET_ERR_ARG;
-    g_wgrad_bm128 = allow_bm128 & 1; g_wgrad_smallp = !(allow_bm128 & 2); g_wgrad_bkw = (allow_bm128 & 4) ? 32 : 16;
-    g_wgrad3 = !(allow_bm128 & 8);
-    g_wgrad3_bkw = (allow_bm128 & 16) ? 32 : 16;
-    g_wgrad3s = !(allow_bm128 & 32);
-    g_wgrad1s = !(allow_bm128 & 64);
-    if (target_blocks < 0) g_wgrad3_target = -target_blocks;      // workgroup target of the three-taps 3x3 kernel
-    else g_wgrad_target = target_blocks;
-    return PHNET_OK;
-}
-
-
-// Tuning aid (process-global): arithmetic of the GEMM kernels.  0 = f32-input MFMA (default), 1 = split-bf16 (igemm.h).
-PHNET_API int phnet_tune_mma(int32_t mode)
-{
-    if (mode < 0 || mode > 3) return PHNET_ERR_ARG;
-    g_mma_mode = mode;
-    g_pf = mode == 3 ? 4 : 1;                                  // the staged-split loop runs with a 4-tile register ring
-    return PHNET_OK;
-}
-
-PHNET_API int phnet_tune_force_k_tile(int32_t kt)
-{
-    if (kt == -1 || kt == -2) { g_uniform_tap = kt == -2; return PHNET_OK; }     // -1: uniform-tap variant off, -2: on again
-    if (kt == -5 || kt == -6) { g_taps3 = kt == -6; return PHNET_OK; }          // -5: three-taps 3x3 forward / dgrad kernel off, -6: on again
-    if (kt == -32 || kt == -64) { g_deep_kt3 = -kt; return PHNET_OK; }
-    if (kt == -101 || kt == -102 || kt == -104) { g_pf = -kt - 100; return PHNET_OK; }
-    if (kt == -200 || kt == -201) { g_buf_loads = -kt - 200; return PHNET_OK; }
-    if (kt != 0 && kt != 16 && kt != 32 && kt != 64) return PHNET_ERR_ARG;
-    g_force_kt = kt;
-    return PHNET_OK;
+    ConvShape g;
+    if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad) || N < 1 || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
+    if (dgrad ? (stride > 2 || !dgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) : !fwd_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g))
+        return PHNET_ERR_ARG;
+    const ConvPick p = pick_conv(g, dgrad != 0, ws_bytes > 0, (size_t)ws_bytes);
+    *splits = p.splits;
+    return conv_kernel_name(p, name, name_cap);
 }
 
 // Forward convolution / linear.  x NHWC [N][Hi][Wi][Ci], w OHWI [Co][R][S][Ci], bias [Co] or NULL,
@@ -1607,16 +1626,10 @@ PHNET_API int phnet_conv2d_fwd(const float* x, const float* w, const float* bias
                                int32_t stride, int32_t pad, int32_t relu,
                                void* workspace, uint64_t ws_bytes, void* stream)
 {
-    if (N < 0 || Hi < 1 || Wi < 1 || Ci < 4 || Co < 4 || (Ci & 3) || (Co & 3) || R < 1 || S < 1 || stride < 1 || pad < 0)
-        return PHNET_ERR_ARG;
+    ConvShape g;
+    if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad)) return PHNET_ERR_ARG;
     if (N == 0) return PHNET_OK;
-    if (!x || !w || !y) return PHNET_ERR_ARG;
-    ConvShape g{};
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ci = Ci; g.Co = Co; g.R = R; g.S = S;
-    g.Ho = (Hi + 2 * pad - R) / stride + 1;
-    g.Wo = (Wi + 2 * pad - S) / stride + 1;
-    if (g.Ho < 1 || g.Wo < 1) return PHNET_ERR_ARG;
-    g.stride = stride; g.pad = pad; g.in_dil = 1;
+    if (!x || !w || !y || !fwd_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) return PHNET_ERR_ARG;
     return launch_conv<false>(x, w, bias, nullptr, y, (float*)workspace, ws_bytes, g, relu, (hipStream_t)stream);
 }
 
@@ -1641,17 +1654,11 @@ PHNET_API int phnet_conv2d_fwd_fused(const float* x, const float* w, const float
                                      int32_t stride, int32_t pad, int32_t relu,
                                      void* workspace, uint64_t ws_bytes, void* stream)
 {
-    if (N < 0 || Hi < 1 || Wi < 1 || Ci < 4 || Co < 4 || (Ci & 3) || (Co & 3) || R < 1 || S < 1 || stride < 1 || pad < 0)
-        return PHNET_ERR_ARG;
+    ConvShape g;
+    if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad)) return PHNET_ERR_ARG;
     if (stats && (bias || addend || relu || (Co & (Co - 1)) || Co > 1024)) return PHNET_ERR_ARG;
     if (N == 0) return PHNET_OK;
-    if (!x || !w || !y) return PHNET_ERR_ARG;
-    ConvShape g{};
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ci = Ci; g.Co = Co; g.R = R; g.S = S;
-    g.Ho = (Hi + 2 * pad - R) / stride + 1;
-    g.Wo = (Wi + 2 * pad - S) / stride + 1;
-    if (g.Ho < 1 || g.Wo < 1) return PHNET_ERR_ARG;
-    g.stride = stride; g.pad = pad; g.in_dil = 1;
+    if (!x || !w || !y || !fwd_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) return PHNET_ERR_ARG;
     return launch_conv<false>(x, w, bias, addend, y, (float*)workspace, ws_bytes, g, relu, (hipStream_t)stream, stats);
 }
 
@@ -1661,24 +1668,13 @@ PHNET_API int phnet_conv2d_dgrad(const float* dy, const float* w, const float* a
                                  int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S,
                                  int32_t stride, int32_t pad, void* workspace, uint64_t ws_bytes, void* stream)
 {
-    if (N < 0 || Hi < 1 || Wi < 1 || Ci < 4 || Co < 4 || (Ci & 3) || (Co & 3) || R < 1 || S < 1 || stride < 1 || pad < 0)
-        return PHNET_ERR_ARG;
+    ConvShape g;
+    if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad)) return PHNET_ERR_ARG;
     if (stride > 2) return PHNET_ERR_ARG;          // the data gradient supports strides 1 and 2 (all the model has)
     if (N == 0) return PHNET_OK;
-    if (!dy || !w || !dx) return PHNET_ERR_ARG;
-    ConvShape g{};
-    g.N = N;
-    g.Hi = (Hi + 2 * pad - R) / stride + 1;      // A-side image = dY
-    g.Wi = (Wi + 2 * pad - S) / stride + 1;
-    g.Ci = Co;
-    g.Ho = Hi; g.Wo = Wi; g.Co = Ci;              // GEMM output = dX
-    g.R = R; g.S = S;
-    g.stride = 1; g.pad = R - 1 - pad; g.in_dil = stride;
-    if (R != S && (S - 1 - pad) != g.pad) return PHNET_ERR_ARG;   // square padding only
-    if (g.pad < 0) return PHNET_ERR_ARG;
+    if (!dy || !w || !dx || !dgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) return PHNET_ERR_ARG;
     return launch_conv<true>(dy, w, nullptr, addend, dx, (float*)workspace, ws_bytes, g, 0, (hipStream_t)stream);
 }
-
 // Weight gradient.  dw OHWI [Co][R][S][Ci] is overwritten (accumulate=0) or added to (accumulate=1).
 // workspace must hold splits*Co*R*S*Ci floats; query with phnet_conv2d_wgrad_workspace.
 static long wgrad_splits(long P, long Co, long NC, int* bm_out)
@@ -1686,9 +1682,9 @@ static long wgrad_splits(long P, long Co, long NC, int* bm_out)
     // measured (bench_conv.py --trunk --wgrad, reduce included): on a 5-frame clip 128-row tiles win at Co = 128 only (73 vs 79 us);
     // at Co = 256 / 512 (5000 / 1250 pixels) the 64x64 tile with more splits is 5 / 3 us faster; with 8 clips per step
     // (40000 / 10000 pixels) the 128-row tile wins everywhere (step 129.7 vs 132.4 ms)
-    const int bm = (Co >= 128 && (Co < 256 || P > 8192) && g_wgrad_bm128) ? 128 : 64;
+    const int bm = (Co >= 128 && (Co < 256 || P > 8192) && tuning().wgrad_bm128) ? 128 : 64;
     const long tiles = ceil_div64(Co, bm) * ceil_div64(NC, 64);
-    const long target = tiles >= 64 ? max((long)g_wgrad_target, (long)1250) : (long)g_wgrad_target;   // measured: bench_conv --wgrad
+    const long target = tiles >= 64 ? max((long)tuning().wgrad_target, (long)1250) : (long)tuning().wgrad_target;   // measured: bench_conv --wgrad
     long splits = max((long)1, min((long)256, target / max((long)1, tiles)));
     splits = max((long)1, min(splits, P / 64));
     // the M=240 linears of the lane head (15 K steps in all): with >= 32 tiles a split only adds a reduce launch;
@@ -1701,13 +1697,13 @@ static long wgrad_splits(long P, long Co, long NC, int* bm_out)
 // the three-taps kernel (conv_wgrad3x3_kernel): 3x3 / stride 1 / pad 1, channel counts in whole 64-tiles, bf16x3 arithmetic
 static bool wgrad3_applies(long P, int Hi, int Wi, int Ci, int Co, int R, int S, int stride, int pad)
 {
-    return g_wgrad3 && g_mma_mode == 3 && R == 3 && S == 3 && stride == 1 && pad == 1 && (Ci & 63) == 0 && (Co & 63) == 0 &&
+    return tuning().wgrad3 && tuning().mma_mode == 3 && R == 3 && S == 3 && stride == 1 && pad == 1 && (Ci & 63) == 0 && (Co & 63) == 0 &&
            Wi >= BK && P >= 64 && P * (long)max(Ci, Co) * 4 < 0x7fffffffL;
 }
 static long wgrad3_splits(long P, long Co, long Ci)
 {
     const long tiles = (Co / 64) * (Ci / 64) * 3;
-    return max((long)1, min(min((long)256, P / 64), (g_wgrad3_target + tiles / 2) / tiles));
+    return max((long)1, min(min((long)256, P / 64), (tuning().wgrad3_target + tiles / 2) / tiles));
 }
 
 PHNET_API uint64_t phnet_conv2d_wgrad_workspace(int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co,
@@ -1721,6 +1717,81 @@ PHNET_API uint64_t phnet_conv2d_wgrad_workspace(int32_t N, int32_t Hi, int32_t W
     return (uint64_t)(splits * (Co * NC + Co) * sizeof(float));
 }
 
+// What one weight-gradient call launches.  Decided once (pick_wgrad); phnet_conv2d_wgrad launches it, wgrad_kernel_name spells it.
+enum class WgradFamily { SmallP, ThreeTapsPC, ThreeTaps, ManyRowsPC, Generic };     // linear_wgrad_smallp | wgrad3s | conv_wgrad3x3 | wgrad1s | conv_wgrad
+struct WgradPick {
+    WgradFamily family;
+    int bm, bkw, mma;                    // output rows per tile; pixels per K step (0: the whole range at once); arithmetic
+    long splits;
+};
+
+static bool wgrad_shape(int N, int Hi, int Wi, int Ci, int Co, int R, int S, int stride, int pad, WgradShape* g)
+{
+    *g = WgradShape{};
+    g->N = N; g->Hi = Hi; g->Wi = Wi; g->Ci = Ci; g->Co = Co; g->R = R; g->S = S; g->stride = stride; g->pad = pad;
+    g->Ho = (Hi + 2 * pad - R) / stride + 1;
+    g->Wo = (Wi + 2 * pad - S) / stride + 1;
+    return conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad);
+}
+
+static WgradPick pick_wgrad(const WgradShape& g, bool has_dbias, bool has_ws, uint64_t ws_bytes)
+{
+    const Tuning& tn = tuning();
+    const int Ci = g.Ci, Co = g.Co;
+    const long P = (long)g.N * g.Ho * g.Wo, NC = (long)g.R * g.S * Ci;
+    const bool linear = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0;
+    auto fit = [&](long splits) {                                        // the split factor whose partial sums the workspace holds
+        const long row = (long)Co * NC + Co;
+        while (splits > 1 && (!has_ws || (uint64_t)(splits * row * sizeof(float)) > ws_bytes)) --splits;
+        return splits;
+    };
+    // Linear over few rows with up to a few hundred output tiles (with thousands of tiles the generic kernel keeps several
+    // workgroups per CU in flight, which hides the same latency; this one needs 139 KB of LDS = one workgroup per CU)
+    if (linear && P <= SMALLP_MAX && tn.wgrad_smallp && ceil_div64(Co, 64) * ceil_div64(Ci, 64) < tn.smallp_max_tiles)
+        return {WgradFamily::SmallP, 64, 0, tn.mma_mode == 1 ? 1 : 0, 1};
+    if (wgrad3_applies(P, g.Hi, g.Wi, Ci, Co, g.R, g.S, g.stride, g.pad)) {
+        const long splits = fit(wgrad3_splits(P, Co, Ci));
+        // producer / consumer kernel: no bias gradient, and an image holds >= one K step
+        if (tn.wgrad3s && !has_dbias && (long)g.Hi * g.Wi >= phnet_wgrad3s_kstep()) return {WgradFamily::ThreeTapsPC, 64, phnet_wgrad3s_kstep(), 3, splits};
+        return {WgradFamily::ThreeTaps, 64, tn.wgrad3_bkw == 16 ? 16 : 32, 3, splits};
+    }
+    // Linear / 1x1 layers over many rows with >= 64 tiles of 128 x 128: the producer / consumer kernel (csrc/wgrad1s.hip)
+    if (tn.wgrad1s && tn.mma_mode == 3 && linear && (Co & 127) == 0 && (Ci & 127) == 0 && P >= 256 &&
+        (long)(Co / 128) * (Ci / 128) >= 64 && P * (long)max(Ci, Co) * 4 < 0x7fffffffL) {
+        const long tiles = (long)(Co / 128) * (Ci / 128);
+        return {WgradFamily::ManyRowsPC, 128, phnet_wgrad1s_kstep(), 3, fit(max((long)1, min((long)(P / 128), (long)256 / tiles)))};
+    }
+    int bm = 64;
+    const long splits = fit(wgrad_splits(P, Co, NC, &bm));
+    return {WgradFamily::Generic, bm, (tn.mma_mode == 3 && tn.wgrad_bkw == 32) ? 32 : BK, tn.mma_mode, splits};
+}
+
+// the instantiation the switch of phnet_conv2d_wgrad below launches for a pick, as rocprofv3 spells it
+static int wgrad_kernel_name(const WgradPick& p, char* name, int cap)
+{
+    int n;
+    switch (p.family) {
+    case WgradFamily::SmallP: n = snprintf(name, (size_t)cap, "linear_wgrad_smallp_kernel<64, 64, %d>", p.mma); break;
+    case WgradFamily::ThreeTapsPC: n = snprintf(name, (size_t)cap, "wgrad3s_kernel<%d>", p.bkw / BK); break;
+    case WgradFamily::ThreeTaps: n = snprintf(name, (size_t)cap, "conv_wgrad3x3_kernel<4, %d>", p.bkw); break;
+    case WgradFamily::ManyRowsPC: n = snprintf(name, (size_t)cap, "wgrad1s_kernel"); break;
+    default: n = snprintf(name, (size_t)cap, "conv_wgrad_kernel<%d, 64, %d, %d, %d, %s>", p.bm, p.mma, p.bkw,
+                          p.mma == 3 ? (p.bkw == 32 ? 2 : 4) : 1, p.mma == 3 ? "true" : "false");
+    }
+    return n < cap ? PHNET_OK : PHNET_ERR_ARG;
+}
+
+// Host-only query: the kernel instantiation phnet_conv2d_wgrad launches for the same shape arguments, and its split factor.
+PHNET_API int phnet_conv2d_wgrad_kernel(int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S, int32_t stride,
+                                        int32_t pad, int32_t has_dbias, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits)
+{
+    WgradShape g;
+    if (!wgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g) || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
+    const WgradPick p = pick_wgrad(g, has_dbias != 0, ws_bytes > 0, ws_bytes);
+    *splits = (int32_t)p.splits;
+    return wgrad_kernel_name(p, name, name_cap);
+}
+
 // dw OHWI [Co][R][S][Ci] and (optionally) dbias [Co] = sum of dy over all pixels are overwritten (accumulate=0) or
 // added to (accumulate=1).  workspace: phnet_conv2d_wgrad_workspace bytes (split-K partial sums; unused when the
 // problem runs unsplit).
@@ -1729,19 +1800,17 @@ PHNET_API int phnet_conv2d_wgrad(const float* dy, const float* x, float* dw, flo
                                  int32_t stride, int32_t pad, int32_t accumulate,
                                  void* workspace, uint64_t ws_bytes, void* stream)
 {
-    if (N < 0 || Hi < 1 || Wi < 1 || Ci < 4 || Co < 4 || (Ci & 3) || (Co & 3) || R < 1 || S < 1 || stride < 1 || pad < 0)
-        return PHNET_ERR_ARG;
-    if (!dy || !x || !dw) return PHNET_ERR_ARG;
-    WgradShape g{};
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ci = Ci; g.Co = Co; g.R = R; g.S = S; g.stride = stride; g.pad = pad;
-    g.Ho = (Hi + 2 * pad - R) / stride + 1;
-    g.Wo = (Wi + 2 * pad - S) / stride + 1;
+    WgradShape g;
+    if (!wgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g) || !dy || !x || !dw) return PHNET_ERR_ARG;
+    const WgradPick p = pick_wgrad(g, dbias != nullptr, workspace != nullptr, ws_bytes);
     const long P = (long)N * g.Ho * g.Wo, NC = (long)R * S * Ci;
     hipStream_t st = (hipStream_t)stream;
-    // Linear over few rows with up to a few hundred output tiles (with thousands of tiles the generic kernel keeps several
-    // workgroups per CU in flight, which hides the same latency; this one needs 139 KB of LDS = one workgroup per CU)
-    if (R == 1 && S == 1 && stride == 1 && pad == 0 && P <= SMALLP_MAX && g_wgrad_smallp &&
-        ceil_div64(Co, 64) * ceil_div64(Ci, 64) < g_smallp_max_tiles) {
+    const int want_bias = dbias != nullptr;
+    float* out = p.splits > 1 ? (float*)workspace : dw;
+    g.splits = (int)p.splits;
+    if (p.bkw) g.pix_per_split = (int)(ceil_div64(ceil_div64(max(P, (long)1), p.bkw), p.splits) * p.bkw);
+    switch (p.family) {
+    case WgradFamily::SmallP: {
         const int P16 = ((int)P + 15) & ~15;
         const size_t lds = (size_t)P16 * (64 + 4) * 2 * sizeof(float);
         static bool attr = false;
@@ -1753,36 +1822,21 @@ PHNET_API int phnet_conv2d_wgrad(const float* dy, const float* x, float* dw, flo
             attr = true;
         }
         const long tiles = ceil_div64(Co, 64) * ceil_div64(Ci, 64);
-        if (g_mma_mode == 1)
+        if (p.mma == 1)
             hipLaunchKernelGGL((linear_wgrad_smallp_kernel<64, 64, 1>), dim3((unsigned)tiles), dim3(THREADS), lds, st, dy, x, dw, dbias,
-                               (int)P, Co, Ci, dbias != nullptr, accumulate);
+                               (int)P, Co, Ci, want_bias, accumulate);
         else
-        hipLaunchKernelGGL((linear_wgrad_smallp_kernel<64, 64, 0>), dim3((unsigned)tiles), dim3(THREADS), lds, st, dy, x, dw, dbias,
-                           (int)P, Co, Ci, dbias != nullptr, accumulate);
-        return phnet_launch_status();
+            hipLaunchKernelGGL((linear_wgrad_smallp_kernel<64, 64, 0>), dim3((unsigned)tiles), dim3(THREADS), lds, st, dy, x, dw, dbias,
+                               (int)P, Co, Ci, want_bias, accumulate);
+        break;
     }
-    if (wgrad3_applies(P, Hi, Wi, Ci, Co, R, S, stride, pad)) {
-        long splits = wgrad3_splits(P, Co, Ci);
-        const long row = (long)Co * NC + Co;
-        while (splits > 1 && (!workspace || (uint64_t)(splits * row * sizeof(float)) > ws_bytes)) --splits;
-        const bool pc = g_wgrad3s && !dbias && (long)Hi * Wi >= phnet_wgrad3s_kstep();      // producer / consumer kernel (an image holds >= one K step)
-        const int bkw = pc ? phnet_wgrad3s_kstep() : g_wgrad3_bkw == 16 ? 16 : 32;
-        const long psteps = ceil_div64(P, bkw);
-        g.splits = (int)splits;
-        g.pix_per_split = (int)(ceil_div64(psteps, splits) * bkw);
-        float* out = splits > 1 ? (float*)workspace : dw;
-        if (pc) {
-            Wgrad3sShape s{N, Hi, Wi, Ci, Co, g.splits, g.pix_per_split};
-            const int rc = phnet_wgrad3s_launch(dy, x, out, s, accumulate, st);
-            if (rc != PHNET_OK) return rc;
-            if (splits > 1) {
-                const long nw = (long)Co * NC, nb = Co;
-                hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((nw + nb) >> 2, 64)), dim3(256), 0, st,
-                                   (const float*)workspace, dw, (float*)nullptr, nw, nb, (int)splits, accumulate);
-            }
-            return phnet_launch_status();
-        }
-        dim3 grid((unsigned)((Co / 64) * (Ci / 64) * 3), 1, (unsigned)splits);
+    case WgradFamily::ThreeTapsPC: {
+        const int rc = phnet_wgrad3s_launch(dy, x, out, Wgrad3sShape{N, Hi, Wi, Ci, Co, g.splits, g.pix_per_split}, accumulate, st);
+        if (rc != PHNET_OK) return rc;
+        break;
+    }
+    case WgradFamily::ThreeTaps: {
+        dim3 grid((unsigned)((Co / 64) * (Ci / 64) * 3), 1, (unsigned)p.splits);
         static bool attr = false;
         if (!attr) {
             if (hipFuncSetAttribute((const void*)conv_wgrad3x3_kernel<4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, Wgrad3Lds<16>::BYTES) != hipSuccess ||
@@ -1790,70 +1844,39 @@ PHNET_API int phnet_conv2d_wgrad(const float* dy, const float* x, float* dw, flo
                 return PHNET_ERR_LAUNCH;
             attr = true;
         }
-        if (bkw == 16)
-            hipLaunchKernelGGL((conv_wgrad3x3_kernel<4, 16>), grid, dim3(W3_THREADS), Wgrad3Lds<16>::BYTES, st, dy, x, out, dbias, g, dbias != nullptr, accumulate);
+        if (p.bkw == 16)
+            hipLaunchKernelGGL((conv_wgrad3x3_kernel<4, 16>), grid, dim3(W3_THREADS), Wgrad3Lds<16>::BYTES, st, dy, x, out, dbias, g, want_bias, accumulate);
         else
-            hipLaunchKernelGGL((conv_wgrad3x3_kernel<4, 32>), grid, dim3(W3_THREADS), Wgrad3Lds<32>::BYTES, st, dy, x, out, dbias, g, dbias != nullptr, accumulate);
-        if (splits > 1) {
-            const long nw = (long)Co * NC, nb = Co;
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((nw + nb) >> 2, 64)), dim3(256), 0, st,
-                               (const float*)workspace, dw, dbias, nw, nb, (int)splits, accumulate);
-        }
-        return phnet_launch_status();
+            hipLaunchKernelGGL((conv_wgrad3x3_kernel<4, 32>), grid, dim3(W3_THREADS), Wgrad3Lds<32>::BYTES, st, dy, x, out, dbias, g, want_bias, accumulate);
+        break;
     }
-    // Linear / 1x1 layers over many rows with >= 64 tiles of 128 x 128: the producer / consumer kernel (csrc/wgrad1s.hip)
-    if (g_wgrad1s && g_mma_mode == 3 && R == 1 && S == 1 && stride == 1 && pad == 0 && (Co & 127) == 0 && (Ci & 127) == 0 && P >= 256 &&
-        (long)(Co / 128) * (Ci / 128) >= 64 && P * (long)max(Ci, Co) * 4 < 0x7fffffffL) {
-        const long tiles1 = (long)(Co / 128) * (Ci / 128);
-        long splits1 = max((long)1, min((long)(P / 128), (long)256 / tiles1));
-        const long row = (long)Co * NC + Co;
-        while (splits1 > 1 && (!workspace || (uint64_t)(splits1 * row * sizeof(float)) > ws_bytes)) --splits1;
-        const int ks = phnet_wgrad1s_kstep();
-        Wgrad1sShape s1{(int)P, Ci, Co, (int)splits1, (int)(ceil_div64(ceil_div64(P, ks), splits1) * ks)};
-        const int rc = phnet_wgrad1s_launch(dy, x, splits1 > 1 ? (float*)workspace : dw, dbias, s1, accumulate, st);
+    case WgradFamily::ManyRowsPC: {
+        const int rc = phnet_wgrad1s_launch(dy, x, out, dbias, Wgrad1sShape{(int)P, Ci, Co, g.splits, g.pix_per_split}, accumulate, st);
         if (rc != PHNET_OK) return rc;
-        if (splits1 > 1) {
-            const long nw = (long)Co * NC, nb = Co;
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((nw + nb) >> 2, 64)), dim3(256), 0, st,
-                               (const float*)workspace, dw, dbias, nw, nb, (int)splits1, accumulate);
-        }
-        return phnet_launch_status();
+        break;
     }
-    int bm = 64;
-    const int bn = 64;
-    long splits = wgrad_splits(P, Co, NC, &bm);
-    const long tiles = ceil_div64(Co, bm) * ceil_div64(NC, bn);
-    const long row = (long)Co * NC + Co;
-    while (splits > 1 && (!workspace || (uint64_t)(splits * row * sizeof(float)) > ws_bytes)) --splits;
-    const int bkw = (g_mma_mode == 3 && g_wgrad_bkw == 32) ? 32 : BK;      // pixels per K step of the kernel picked below
-    const long psteps = ceil_div64(max(P, (long)1), bkw);
-    g.splits = (int)splits;
-    g.pix_per_split = (int)(ceil_div64(psteps, splits) * bkw);
-    float* out = splits > 1 ? (float*)workspace : dw;
-    dim3 grid((unsigned)tiles, 1, (unsigned)splits);
-    const int want_bias = dbias != nullptr;
-    if (g_mma_mode == 3 && bkw == 32 && bm == 128)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 3, 32, 2, true>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (g_mma_mode == 3 && bkw == 32)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 3, 32, 2, true>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (g_mma_mode == 3 && bm == 128)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 3, 16, 4, true>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (g_mma_mode == 3)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 3, 16, 4, true>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (bm == 128 && g_mma_mode == 2)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 2>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (g_mma_mode == 2)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (bm == 128 && g_mma_mode == 1)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 1>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (g_mma_mode == 1)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 1>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else if (bm == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 64>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate);
-    if (splits > 1) {
+    case WgradFamily::Generic: {
+        dim3 grid((unsigned)(ceil_div64(Co, p.bm) * ceil_div64(NC, 64)), 1, (unsigned)p.splits);
+#define PHNET_LAUNCH_WGRAD(...)                                                                                         \
+    hipLaunchKernelGGL((conv_wgrad_kernel<__VA_ARGS__>), grid, dim3(THREADS), 0, st, dy, x, out, dbias, g, want_bias, accumulate)
+        if (p.mma == 3 && p.bkw == 32 && p.bm == 128) PHNET_LAUNCH_WGRAD(128, 64, 3, 32, 2, true);
+        else if (p.mma == 3 && p.bkw == 32) PHNET_LAUNCH_WGRAD(64, 64, 3, 32, 2, true);
+        else if (p.mma == 3 && p.bm == 128) PHNET_LAUNCH_WGRAD(128, 64, 3, 16, 4, true);
+        else if (p.mma == 3) PHNET_LAUNCH_WGRAD(64, 64, 3, 16, 4, true);
+        else if (p.bm == 128 && p.mma == 2) PHNET_LAUNCH_WGRAD(128, 64, 2);
+        else if (p.mma == 2) PHNET_LAUNCH_WGRAD(64, 64, 2);
+        else if (p.bm == 128 && p.mma == 1) PHNET_LAUNCH_WGRAD(128, 64, 1);
+        else if (p.mma == 1) PHNET_LAUNCH_WGRAD(64, 64, 1);
+        else if (p.bm == 128) PHNET_LAUNCH_WGRAD(128, 64);
+        else PHNET_LAUNCH_WGRAD(64, 64);
+#undef PHNET_LAUNCH_WGRAD
+        break;
+    }
+    }
+    if (p.splits > 1) {                                                  // the partial sums of every family share one layout
         const long nw = (long)Co * NC, nb = Co;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((nw + nb) >> 2, 64)), dim3(256), 0, st,
-                           (const float*)workspace, dw, dbias, nw, nb, (int)splits, accumulate);
+                           (const float*)workspace, dw, dbias, nw, nb, (int)p.splits, accumulate);
     }
     return phnet_launch_status();
 }
@@ -1884,13 +1907,34 @@ PHNET_API int phnet_pad_channels(const float* src, float* dst, int64_t rows, int
 // ---- fused backward of a Linear layer over few rows ------------------------------------------------------------------
 static bool linear_bwd_fusable(long M, long K, long N)
 {
-    if (!g_wgrad_smallp || M < 1 || M > SMALLP_MAX || (K & 3) || (N & 3) || K < 4 || N < 4) return false;
+    if (!tuning().wgrad_smallp || M < 1 || M > SMALLP_MAX || (K & 3) || (N & 3) || K < 4 || N < 4) return false;
     const long wt = ceil_div64(N, 64) * ceil_div64(K, 64), dt = ceil_div64(M, 64) * ceil_div64(K, 64);
-    return wt < g_smallp_max_tiles && N <= 640 && dt <= 256;          // dgrad stays unsplit: reduction length N <= 640 (gate MLP: 576)
+    return wt < tuning().smallp_max_tiles && N <= 640 && dt <= 256;   // dgrad stays unsplit: reduction length N <= 640 (gate MLP: 576)
 }
 
 // 1 when phnet_linear_bwd runs (M, K, N) as ONE launch; 0: use phnet_conv2d_dgrad + phnet_conv2d_wgrad instead.
 PHNET_API int phnet_linear_bwd_fusable(int64_t M, int64_t K, int64_t N) { return linear_bwd_fusable(M, K, N) ? 1 : 0; }
+
+// linear_bwd_fused_kernel<uni, relu, mma>: what phnet_linear_bwd launches and what linear_bwd_kernel_name spells
+struct LinearBwdPick { bool uni, relu; int mma; };
+
+static LinearBwdPick pick_linear_bwd(long N, bool has_relu_mask)
+{
+    return {N % 64 == 0 && tuning().uniform_tap, has_relu_mask, tuning().mma_mode == 1 ? 1 : 0};
+}
+
+static int linear_bwd_kernel_name(const LinearBwdPick& p, char* name, int cap)
+{
+    return snprintf(name, (size_t)cap, "linear_bwd_fused_kernel<%s, %s, %d>", p.uni ? "true" : "false", p.relu ? "true" : "false", p.mma) < cap
+               ? PHNET_OK : PHNET_ERR_ARG;
+}
+
+// Host-only query: the kernel instantiation phnet_linear_bwd launches for the same shape.
+PHNET_API int phnet_linear_bwd_kernel(int32_t M, int32_t K, int32_t N, int32_t has_relu_mask, char* name, int32_t name_cap)
+{
+    if (!linear_bwd_fusable(M, K, N) || !name || name_cap < 1) return PHNET_ERR_ARG;
+    return linear_bwd_kernel_name(pick_linear_bwd(N, has_relu_mask != 0), name, name_cap);
+}
 
 // Backward of y = x w^T (+ b) for few rows, one launch: dx [M][K] = dy w;  dw [N][K] and dbias [N] (optional) = dy^T x,
 // column sums of dy - overwritten or, with accumulate = 1, added to.  dy [M][N], x [M][K], w [N][K], all row-major.
@@ -1923,18 +1967,18 @@ PHNET_API int phnet_linear_bwd(const float* dy, const float* x, const float* w, 
         attr = true;
     }
     hipStream_t st = (hipStream_t)stream;
-    const bool uni = N % 64 == 0 && g_uniform_tap;
+    const LinearBwdPick p = pick_linear_bwd(N, relu_y != nullptr);
 #define PHNET_LAUNCH_BWD_(U_, A_, MMA_)                                                                                 \
     hipLaunchKernelGGL((linear_bwd_fused_kernel<U_, A_, MMA_>), dim3(dt + wt), dim3(THREADS), lds, st, dy, w, x, relu_y, dx, \
                        dw, dbias, g, dt, (int)M, (int)N, (int)K, dbias != nullptr, accumulate)
 #define PHNET_LAUNCH_BWD(U_, A_)                                                                                        \
     do {                                                                                                                \
-        if (g_mma_mode == 1) PHNET_LAUNCH_BWD_(U_, A_, 1);                                                              \
+        if (p.mma == 1) PHNET_LAUNCH_BWD_(U_, A_, 1);                                                                   \
         else PHNET_LAUNCH_BWD_(U_, A_, 0);                                                                              \
     } while (0)
-    if (uni && relu_y) PHNET_LAUNCH_BWD(true, true);
-    else if (uni) PHNET_LAUNCH_BWD(true, false);
-    else if (relu_y) PHNET_LAUNCH_BWD(false, true);
+    if (p.uni && p.relu) PHNET_LAUNCH_BWD(true, true);
+    else if (p.uni) PHNET_LAUNCH_BWD(true, false);
+    else if (p.relu) PHNET_LAUNCH_BWD(false, true);
     else PHNET_LAUNCH_BWD(false, false);
 #undef PHNET_LAUNCH_BWD
 #undef PHNET_LAUNCH_BWD_

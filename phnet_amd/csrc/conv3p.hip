@@ -15,7 +15,9 @@
 //    shifted image row staged once - split into bf16 planes on the way - and multiplied by the three taps dx).
 //
 // Roofline: MFMA (bf16 pipe, 6 MFMAs per f32-exact product: 416.7 TFLOP/s algorithmic); algorithmic FLOP = 2 * M * Co * 9Ci.
+#include <cstdio>
 #include "igemm.h"
+#include "tuning.h"
 
 using namespace igemm;
 
@@ -347,9 +349,6 @@ __global__ __launch_bounds__(256) void conv3p_reduce_kernel(const float* __restr
 
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
-int g_p3_target = 512;          // workgroups a launch is topped up to by split-K (tuning aid: phnet_conv3p_tune): two per CU, evenly
-int g_p3_wide = 1;              // 128-column workgroup tile (64 x 64 per wave) where the output has >= 128 channels
-
 struct P3Plan { long tiles; int fn, splits, units_per_split; };
 
 // Measured on MI355X (tests/tools/bench_conv3p.py, one 5-frame clip): what matters at these sizes is that the workgroups of a
@@ -360,18 +359,24 @@ P3Plan p3_plan(long M, int Ca, int Nn, size_t ws_bytes)
     P3Plan p;
     // the 128-column tile halves the A-side LDS traffic per MFMA but doubles the weight bytes a wave streams per step: measured
     // +4 % on layer2 (20000 pixels x 128), nothing on layer3, -15 % on layer4 (1250 x 512: few tiles, 14 MB of weights)
-    p.fn = (g_p3_wide && Nn % 128 == 0 && M >= 16384) ? 2 : 1;
+    p.fn = (tuning().p3_wide && Nn % 128 == 0 && M >= 16384) ? 2 : 1;
     p.tiles = cdiv(M, P3_BM) * (Nn / (64 * p.fn));
     const int units = 3 * (Ca / 16);
     int splits = 1;
-    if (ws_bytes > 0 && p.tiles * 2 <= g_p3_target) {
-        splits = (int)min((long)8, (long)g_p3_target / p.tiles);
+    if (ws_bytes > 0 && p.tiles * 2 <= tuning().p3_target) {
+        splits = (int)min((long)8, (long)tuning().p3_target / p.tiles);
         while (splits > 1 && units / splits < 4) --splits;                     // >= 4 units (192 of K) per split
         while (splits > 1 && (size_t)splits * M * Nn * sizeof(float) > ws_bytes) --splits;
     }
     p.units_per_split = (units + splits - 1) / splits;
     p.splits = (units + p.units_per_split - 1) / p.units_per_split;            // no empty split
     return p;
+}
+
+// the instantiation the launch switch of phnet_conv3p_fwd picks for a plan
+int p3_kernel_name(const P3Plan& p, char* name, int cap)
+{
+    return snprintf(name, (size_t)cap, "conv3p_kernel<%d>", p.fn) < cap ? PHNET_OK : PHNET_ERR_ARG;
 }
 
 bool p3_applies(long M, int Ca, int Nn)
@@ -419,18 +424,13 @@ PHNET_API uint64_t phnet_conv3p_stats_blocks(int64_t M, int32_t Ca, int32_t Nn, 
     return (uint64_t)(p.splits > 1 ? cdiv((long)M * Nn / 4, 256 * P3_RCH) : cdiv((long)M, P3_BM) * (P3_BM / 64));
 }
 
-PHNET_API int phnet_conv3p_splits(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes)
+// Host-only query: the instantiation phnet_conv3p_fwd launches for this shape (as rocprofv3 spells it) and its split-K factor
+PHNET_API int phnet_conv3p_kernel(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes, char* name, int32_t name_cap, int32_t* splits)
 {
-    if (!p3_applies((long)M, Ca, Nn)) return 0;
-    return p3_plan((long)M, Ca, Nn, (size_t)ws_bytes).splits;
-}
-
-PHNET_API int phnet_conv3p_tune(int32_t target_workgroups)
-{
-    if (target_workgroups == -1 || target_workgroups == -2) { g_p3_wide = target_workgroups == -2; return PHNET_OK; }   // -1: 64-column tiles only
-    if (target_workgroups < 1) return PHNET_ERR_ARG;
-    g_p3_target = target_workgroups;
-    return PHNET_OK;
+    if (!p3_applies((long)M, Ca, Nn) || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
+    const P3Plan p = p3_plan((long)M, Ca, Nn, (size_t)ws_bytes);
+    *splits = p.splits;
+    return p3_kernel_name(p, name, name_cap);
 }
 
 // y = conv3x3(x, w) (+ bias) (+ addend) (ReLU) with w given PACKED (phnet_conv3p_pack, dgrad = 0); or, on the dgrad packing,

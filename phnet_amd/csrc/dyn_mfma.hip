@@ -14,6 +14,7 @@
 // LayerNorm statistics per row: in-lane sum over the lane's columns, then over the 16 lanes of its group (two-pass: mean, then the
 // variance of the centred values, as dynhead.hip).
 #include "common.h"
+#include "tuning.h"
 
 namespace {
 
@@ -522,8 +523,6 @@ __global__ __launch_bounds__(256, 4) void dyn_mfma_bwd_split_kernel(const float*
 
 }  // namespace
 
-int g_dyn_rows = 1;             // forward: one wavefront per (anchor, row fragment); backward: four wavefronts per anchor; phnet_tune_dyn_mfma(2 | ...) switches both off
-
 PHNET_API int phnet_dyn_mfma_applies(int32_t P, int32_t K, int32_t J)
 {
     return P >= 1 && P <= 36 && ((K == 64 && J == 128) || (K == 128 && J == 64));
@@ -535,7 +534,7 @@ PHNET_API int phnet_dyn_mfma_fwd(const float* x, const float* w, const float* ga
 {
     if (N < 1 || !phnet_dyn_mfma_applies(P, K, J) || !x || !w || !gamma || !beta || !y) return PHNET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (g_dyn_rows) {                                           // one wavefront per (anchor, row fragment)
+    if (tuning().dyn_rows) {                                           // one wavefront per (anchor, row fragment)
         const int nfr = (P + 15) / 16;
         const dim3 grid((unsigned)(((long)N * nfr + 3) / 4));
         if (K == 64) hipLaunchKernelGGL((dyn_mfma_fwd_rows_kernel<64, 128>), grid, dim3(256), 0, st, x, w, gamma, beta, y, stats, N, P, nfr, eps);
@@ -555,7 +554,7 @@ PHNET_API int phnet_dyn_mfma_bwd(const float* dy, const float* x, const float* w
 {
     if (N < 1 || !phnet_dyn_mfma_applies(P, K, J) || !dy || !x || !w || !y || !stats || !gamma || !dw || !lnpart) return PHNET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (g_dyn_rows) {                                           // one workgroup (four wavefronts) per anchor
+    if (tuning().dyn_rows) {                                           // one workgroup (four wavefronts) per anchor
         const size_t lds4 = ((size_t)48 * (J + 4) + 6 * J) * sizeof(float);
         if (K == 64) hipLaunchKernelGGL((dyn_mfma_bwd_split_kernel<64, 128>), dim3((unsigned)N), dim3(256), lds4, st, dy, x, w, y, stats, gamma, dx, dw, lnpart, N, P);
         else hipLaunchKernelGGL((dyn_mfma_bwd_split_kernel<128, 64>), dim3((unsigned)N), dim3(256), lds4, st, dy, x, w, y, stats, gamma, dx, dw, lnpart, N, P);

@@ -1,9 +1,10 @@
-import os
 """Tensor-level wrappers over the C-ABI (include/phnet_hip.h): shape checks, output allocation, stream plumbing.
 
 PyTorch is used here only for device memory and the current HIP stream.  No op in this file has a
 fallback: a non-CUDA tensor or a missing library raises.
 """
+import ctypes
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -17,24 +18,12 @@ _WS = {}
 TIMER = None
 
 
-_MMA_MODE = 3        # arithmetic of the GEMM kernels (set_mma_mode; 3 = "bf16x3", the library default); here only used to NAME kernel symbols for bench.py
-
-
-_TAPS3 = True           # mirrors csrc/conv.hip g_taps3 (kernel names of the bench's per-kernel accounting only)
-
-
-def _gemm_symbol(m, co, k, ws_bytes, dgrad, ci_a, in_dil=1, taps3=False):
-    import ctypes
-    bm, bn, sp, kt = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    check(lib().phnet_conv2d_plan(m, co, k, ws_bytes, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(sp), ctypes.byref(kt)),
-          "phnet_conv2d_plan")
-    uni = bm.value == 64 and bn.value == 64 and ci_a % kt.value == 0      # uniform-tap variant (csrc/conv.hip)
-    pf = 4 if _MMA_MODE == 3 else 1                                       # register prefetch ring; buffer loads (launch_conv)
-    buf = uni and _MMA_MODE == 3 and in_dil == 1
-    if taps3 and buf and kt.value == 16 and _TAPS3:                       # three-taps 3x3 / stride-1 kernel (launch_conv)
-        return f"conv3x3s1_kernel<{'true' if dgrad else 'false'}>", sp.value
-    return (f"conv_igemm_kernel<{bm.value}, {bn.value}, {'true' if dgrad else 'false'}, {kt.value}, {'true' if uni else 'false'}, "
-            f"{_MMA_MODE}, {pf}, {'true' if buf else 'false'}>", sp.value)
+def _kernel(query, *shape_args, has_splits=True):
+    """(kernel symbol, split factor) of the launch entry with the same shape arguments, from the library's host-only
+    phnet_*_kernel queries: the decision function that launches the kernel also names it."""
+    name, splits = ctypes.create_string_buffer(96), ctypes.c_int32(0)
+    check(query(*shape_args, name, len(name), *([ctypes.byref(splits)] if has_splits else [])), "kernel query")
+    return name.value.decode(), splits.value
 
 
 def _timed_launch(sym_fn, flops, launch, shape=None, nbytes=None):
@@ -71,6 +60,11 @@ def _req(t: torch.Tensor, dtype=torch.float32, name="tensor"):
 
 
 _WS_RETIRED = []
+
+
+def workspace_buffers() -> dict:
+    """{(device index, slot): tensor} of the live scratch buffers (a copy: tests watch them for growth)."""
+    return dict(_WS)
 
 
 def workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
@@ -164,12 +158,12 @@ def conv2d_fwd(x, w, bias, stride: int, pad: int, relu: bool = False, out: Optio
         if addend is not None:
             _req(addend, name="addend")
             assert addend.shape == out.shape
-        _timed_launch(lambda: _gemm_symbol(m, co, k, need, False, ci, taps3=(r == 3 and s == 3 and stride == 1 and pad == 1)), 2.0 * m * co * k,
+        _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 0, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * m * co * k,
                       lambda: check(lib().phnet_conv2d_fwd_fused(_ptr(x), _ptr(w), _ptr(bias), _ptr(addend), _ptr(out), _ptr(part), n, hi, wi,
                                                                  ci, co, r, s, stride, pad, int(relu), _ptr(ws), need, _stream()),
                                     "phnet_conv2d_fwd_fused"), shape=("fwd", m, co, k, r), nbytes=4.0 * (n * hi * wi * ci + m * co + co * k))
         return (out, (part, nblk)) if stats else out
-    _timed_launch(lambda: _gemm_symbol(m, co, k, need, False, ci, taps3=(r == 3 and s == 3 and stride == 1 and pad == 1)), 2.0 * m * co * k,
+    _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 0, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * m * co * k,
                   lambda: check(lib().phnet_conv2d_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), n, hi, wi, ci, co, r, s, stride,
                                                        pad, int(relu), _ptr(ws), need, _stream()), "phnet_conv2d_fwd"),
                   shape=("fwd", m, co, k, r), nbytes=4.0 * (n * hi * wi * ci + m * co + co * k))
@@ -246,8 +240,7 @@ def conv3p(x: torch.Tensor, packed: torch.Tensor, nn: int, dgrad: bool = False, 
     if addend is not None:
         _req(addend, name="addend")
         assert addend.shape == out.shape
-    # the symbol rocprofv3 sees: <2> = the 128-column tile (csrc/conv3p.hip p3_plan: >= 128 output channels and >= 16384 pixels)
-    _timed_launch(lambda: (f"conv3p_kernel<{2 if (nn % 128 == 0 and m >= 16384) else 1}>", int(lib().phnet_conv3p_splits(m, ca, nn, need))),
+    _timed_launch(lambda: _kernel(lib().phnet_conv3p_kernel, m, ca, nn, need),
                   2.0 * m * nn * 9 * ca,
                   lambda: check(lib().phnet_conv3p_fwd(_ptr(x), _ptr(packed), _ptr(bias), _ptr(addend), _ptr(out), _ptr(part), n, h, w_, ca, nn,
                                                        int(relu), _ptr(ws), need, _stream()), "phnet_conv3p_fwd"),
@@ -265,7 +258,7 @@ def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: O
     need = 8 * n * hi * wi * ci * 4 if n * hi * wi * ci < (1 << 23) else 0
     ws = workspace(need, dy.device) if need else None
     m, k = n * hi * wi, r * s * co
-    _timed_launch(lambda: _gemm_symbol(m, ci, k, need, True, co, stride, taps3=(r == 3 and s == 3 and stride == 1 and pad == 1)), 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * co * r * s * ci,
+    _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 1, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * co * r * s * ci,
                   lambda: check(lib().phnet_conv2d_dgrad(_ptr(dy), _ptr(w), _ptr(addend), _ptr(dx), n, hi, wi, ci, co, r, s, stride,
                                                          pad, _ptr(ws), need, _stream()), "phnet_conv2d_dgrad"),
                   shape=("dgrad", m, ci, k, r), nbytes=4.0 * (dy.numel() + m * ci + co * r * s * ci))
@@ -273,9 +266,6 @@ def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: O
 
 
 CONV3P = os.environ.get("PHNET_CONV3P", "1") != "0"           # packed-weight 3x3 kernel for the trunk / FPN forward and data gradient (trunk.packed_path); bench A/B switch
-_WGRAD3 = True          # mirrors csrc/conv.hip g_wgrad3 (kernel names of the bench's per-kernel accounting only)
-_WGRAD3S = True         # mirrors g_wgrad3s (same purpose)
-_WGRAD1S = True         # mirrors g_wgrad1s
 
 
 def conv2d_wgrad(dy, x, w_shape, stride: int, pad: int, dw: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -291,16 +281,7 @@ def conv2d_wgrad(dy, x, w_shape, stride: int, pad: int, dw: Optional[torch.Tenso
     need = lib().phnet_conv2d_wgrad_workspace(n, hi, wi, ci, co, r, s, stride, pad)
     ws = workspace(need, x.device) if need else None
     ho, wo = conv_out_hw(hi, wi, r, s, stride, pad)
-    smallp = (r == 1 and s == 1 and stride == 1 and pad == 0 and n * ho * wo <= 256 and
-              ((co + 63) // 64) * ((ci + 63) // 64) < 400)                                # few-rows Linear kernel (csrc/conv.hip)
-    taps3 = (_MMA_MODE == 3 and r == 3 and s == 3 and stride == 1 and pad == 1 and ci % 64 == 0 and co % 64 == 0 and wi >= 16 and
-             n * ho * wo >= 64 and _WGRAD3)                                              # three-taps kernel (csrc/conv.hip)
-    _timed_launch(lambda: (f"linear_wgrad_smallp_kernel<64, 64, {1 if _MMA_MODE == 1 else 0}>" if smallp
-                           else "wgrad1s_kernel" if (_WGRAD1S and _MMA_MODE == 3 and r == 1 and s == 1 and stride == 1 and pad == 0 and co % 128 == 0
-                                                     and ci % 128 == 0 and n * ho * wo >= 256 and (co // 128) * (ci // 128) >= 64)
-                           else "wgrad3s_kernel<2>" if taps3 and dbias is None and _WGRAD3S
-                           else "conv_wgrad3x3_kernel<4, 16>" if taps3
-                           else f"conv_wgrad_kernel<{128 if (co >= 128 and (co < 256 or n * ho * wo > 8192)) else 64}, 64, {_MMA_MODE}, 16, {4 if _MMA_MODE == 3 else 1}, {'true' if _MMA_MODE == 3 else 'false'}>", 0),
+    _timed_launch(lambda: _kernel(lib().phnet_conv2d_wgrad_kernel, n, hi, wi, ci, co, r, s, stride, pad, int(dbias is not None), need),
                   2.0 * n * ho * wo * co * r * s * ci,
                   lambda: check(lib().phnet_conv2d_wgrad(_ptr(dy), _ptr(x), _ptr(dw), _ptr(dbias), n, hi, wi, ci, co, r, s, stride,
                                                          pad, int(accumulate), _ptr(ws), need, _stream()), "phnet_conv2d_wgrad"),
@@ -339,8 +320,7 @@ def linear_bwd(dy2d, x2d, w, dw: torch.Tensor, dbias: Optional[torch.Tensor], ac
     m, n = dy2d.shape
     k = x2d.shape[1]
     dx = torch.empty((m, k), dtype=torch.float32, device=dy2d.device)
-    sym = f"linear_bwd_fused_kernel<{'true' if n % 64 == 0 else 'false'}, {'true' if relu_y is not None else 'false'}, {1 if _MMA_MODE == 1 else 0}>"
-    _timed_launch(lambda: (sym, 0), 4.0 * m * n * k,
+    _timed_launch(lambda: _kernel(lib().phnet_linear_bwd_kernel, m, k, n, int(relu_y is not None), has_splits=False), 4.0 * m * n * k,
                   lambda: check(lib().phnet_linear_bwd(_ptr(dy2d), _ptr(x2d), _ptr(w), _ptr(relu_y), _ptr(dx), _ptr(dw), _ptr(dbias), m, k, n,
                                                        int(accumulate), _stream()), "phnet_linear_bwd"), shape=("linbwd", m, n, k, 1))
     return dx
@@ -1158,20 +1138,23 @@ def lane_mask_iou(segs, n_lanes: int, pairs, height: int, width: int, lane_width
 
 def tune_k_tile(code: int) -> None:
     """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on."""
-    global _TAPS3
     check(lib().phnet_tune_force_k_tile(code), "phnet_tune_force_k_tile")
-    if code in (-5, -6):
-        _TAPS3 = code == -6
 
 
 def tune_wgrad(flags: int = 1, target: int = 768) -> None:
     """Benchmark aid (process-global): phnet_tune_wgrad - bit 3 of `flags` switches the three-taps 3x3 weight-gradient kernel off,
     bit 4 gives it 32-pixel steps, bit 5 switches its producer / consumer variant (csrc/wgrad3s.hip) off; a negative `target` is ITS workgroup target, a positive one the generic kernel's."""
-    global _WGRAD3, _WGRAD3S, _WGRAD1S
     check(lib().phnet_tune_wgrad(flags, target), "phnet_tune_wgrad")
-    _WGRAD3 = not (flags & 8)
-    _WGRAD3S = not (flags & 32)
-    _WGRAD1S = not (flags & 64)
+
+
+def tune_reset() -> None:
+    """Every switch of include/phnet_hip_tuning.h (arithmetic mode included) back to its default."""
+    check(lib().phnet_tune_reset(), "phnet_tune_reset")
+
+
+def mma_mode() -> int:
+    """The library's current GEMM arithmetic (phnet_tune_mma code; 3 = "bf16x3")."""
+    return int(lib().phnet_tune_mma_get())
 
 
 def set_mma_mode(mode: str) -> None:
@@ -1181,7 +1164,4 @@ def set_mma_mode(mode: str) -> None:
     f32 value), 6 bf16 MFMAs per product, dropped terms <= 2^-24: the accuracy of "f32" (csrc/igemm.h); "bf16x3" = the same
     exact three-term arithmetic with the split done ONCE while a tile is staged into LDS (bf16 planes, transposed fragment
     reads): the fast form of "split3_bf16"."""
-    global _MMA_MODE
-    code = {"f32": 0, "split_bf16": 1, "split3_bf16": 2, "bf16x3": 3}[mode]
-    check(lib().phnet_tune_mma(code), "phnet_tune_mma")
-    _MMA_MODE = code
+    check(lib().phnet_tune_mma({"f32": 0, "split_bf16": 1, "split3_bf16": 2, "bf16x3": 3}[mode]), "phnet_tune_mma")

@@ -58,7 +58,7 @@ def _is3x3s1(conv: nn.Conv2d) -> bool:
 
 def packed_path() -> bool:
     """The packed-weight 3x3 kernel (csrc/conv3p.hip) runs in the default GEMM arithmetic only."""
-    return K._MMA_MODE == 3 and K.CONV3P
+    return K.CONV3P and K.mma_mode() == 3
 
 
 def _pack_plan(enc, convs):

@@ -331,7 +331,7 @@ def test_many_row_linear_weight_gradient_kernel_vs_fp64(ops, bf16x3, case):
     try:
         dw_generic = ops.conv2d_wgrad(gyd, xd, shape, 1, 0)
     finally:
-        assert lib().phnet_tune_wgrad(1, 768) == 0
+        assert lib().phnet_tune_reset() == 0
     close(dw_generic.view(Co, Ci), want, 2e-5)
     close(dw_nb, dw_generic, 1e-5)
 
@@ -370,19 +370,19 @@ def test_wgrad_three_taps_kernel_vs_fp64(ops, bf16x3, case):
     try:
         close(ops.conv2d_wgrad(gyd, xd, shape, 1, 1), want, 2e-5)
     finally:
-        assert lib().phnet_tune_wgrad(1, 768) == 0
+        assert lib().phnet_tune_reset() == 0
     assert lib().phnet_tune_wgrad(1 | 8, 768) == 0                       # the generic kernel on the same operands
     try:
         dw_generic = ops.conv2d_wgrad(gyd, xd, shape, 1, 1)
     finally:
-        assert lib().phnet_tune_wgrad(1, 768) == 0
+        assert lib().phnet_tune_reset() == 0
     close(dw_generic, want, 2e-5)
     for flags, target in ((1, 64), (1, 1024), (1 | 32, 64), (1 | 32 | 16, 256), (1 | 32 | 16, 1024)):      # other splits of the pixel range, down to
         assert lib().phnet_tune_wgrad(flags, -target) == 0                   # one step; bit 4: 32-pixel instead of 16-pixel steps (bit 5 kernel)
         try:
             close(ops.conv2d_wgrad(gyd, xd, shape, 1, 1), want, 2e-5)
         finally:
-            assert lib().phnet_tune_wgrad(1, -256) == 0
+            assert lib().phnet_tune_reset() == 0
 
 
 @pytest.mark.parametrize("case", [(2, 16, 20, 64, 64), (3, 5, 17, 16, 36), (2, 7, 16, 48, 64), (1, 1, 70, 32, 128), (5, 20, 50, 256, 64),
@@ -425,7 +425,7 @@ def test_conv3x3_three_taps_forward_and_dgrad_vs_fp64(ops, bf16x3, case):
     try:
         g = run()
     finally:
-        assert lib().phnet_tune_force_k_tile(-6) == 0
+        assert lib().phnet_tune_reset() == 0
     for a_, b_ in ((y, g[0]), (yr, g[1]), (dx, g[3]), (dxa, g[4])):
         assert float((a_ - b_).abs().max()) <= 4e-5 * float(b_.abs().max())
 
@@ -711,7 +711,7 @@ def test_dynamic_head_bmm_layernorm_relu(ops, N, P, K, J):
         try:
             y_a, st_a = ops.dyn_bmm_ln_relu_fwd(xd, wd, gd, bd, 1e-5)
         finally:
-            assert lib().phnet_tune_dyn_mfma(1) == 0
+            assert lib().phnet_tune_reset() == 0
         assert torch.equal(y_a, yd) and torch.equal(st_a, stats)
     dx, dw, dg, db = ops.dyn_bmm_ln_relu_bwd(dev(g.float()), xd, wd, yd, stats, gd, 1e-5)
     close(dx, x.grad, 5e-5); close(dw, w.grad, 5e-5); close(dg, ga.grad, 5e-5); close(db, be.grad, 5e-5)
@@ -722,7 +722,7 @@ def test_dynamic_head_bmm_layernorm_relu(ops, N, P, K, J):
         try:
             dx_a, dw_a, dg_a, db_a = ops.dyn_bmm_ln_relu_bwd(dev(g.float()), xd, wd, yd, stats, gd, 1e-5)
         finally:
-            assert lib().phnet_tune_dyn_mfma(1) == 0
+            assert lib().phnet_tune_reset() == 0
         close(dx_a, dx, 2e-6); close(dw_a, dw, 2e-6); close(dg_a, dg, 2e-6); close(db_a, db, 2e-6)
     # accumulate mode adds to the destinations; dx may be skipped
     acc_g, acc_b = torch.ones_like(gd), torch.ones_like(gd)

@@ -785,18 +785,18 @@ def test_workspace_growth_after_graph_capture_keeps_the_graph_valid():
     frames = synth.make_clip(g, 3, seed=21).cuda()
     graph = GraphedInference(model, frames)
     rows0, nums0, anch0 = [t.clone() for t in graph(frames)]
-    before = {k: v.data_ptr() for k, v in K._WS.items()}
+    before = {k: v.data_ptr() for k, v in K.workspace_buffers().items()}
     # every scratch slot is outgrown (what a larger problem in the same process does - eval with more clips, a larger
     # resolution, a second graph at a larger shape), then ops that use the new buffers run
     n_retired = len(K._WS_RETIRED)
-    for (dev_index, slot), buf in list(K._WS.items()):
+    for (dev_index, slot), buf in K.workspace_buffers().items():
         K.workspace(2 * buf.numel() + 1, torch.device("cuda", dev_index), slot)
     x = torch.randn(2, 24, 40, 64, device="cuda")
     w = torch.randn(64, 3, 3, 64, device="cuda") * 0.05
     y = K.conv2d_fwd(x, w, None, 1, 1)
     K.conv2d_wgrad(torch.randn_like(y), x, (64, 3, 3, 64), 1, 1)
     K.bn_fwd(y, torch.ones(64, device="cuda"), torch.zeros(64, device="cuda"), None, None, True, 1e-5, 0.1, None, True)
-    grown = [k for k, v in K._WS.items() if k in before and v.data_ptr() != before[k]]
+    grown = [k for k, v in K.workspace_buffers().items() if k in before and v.data_ptr() != before[k]]
     assert len(grown) == len(before) and len(K._WS_RETIRED) >= n_retired + len(grown)
     sentinels = [torch.full((1 << 20,), 7.0, device="cuda") for _ in range(8)]        # would land in freed scratch memory
     rows1, nums1, anch1 = graph(frames)

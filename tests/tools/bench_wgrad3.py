@@ -41,7 +41,7 @@ def main():
             K.tune_wgrad(f, 768)
             t = timeit(lambda: K.conv2d_wgrad(gy, x, dw.shape, 1, 1, dw=dw, accumulate=True))
             out.append(f"flags {f:2d}: {t:6.1f} us {fl / t / 1e6:6.1f} TF/s")
-        K.tune_wgrad(1, 768)
+        K.tune_reset()
         print(f"{name} ({n}x{h}x{w}x{c}): " + " | ".join(out), flush=True)
 
 
