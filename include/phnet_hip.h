@@ -381,6 +381,17 @@ int phnet_stream_push(const float* feat, const int64_t* anchors_sorted, float* r
                       int32_t* n, int32_t S, int32_t B, int32_t W, int32_t N, int32_t E, int32_t L, void* stream);
 int phnet_stream_select(const float* attn, const uint8_t* has_memory, float* feat, int32_t B, int32_t N, int32_t E, void* stream);
 
+/* ---- streaming inference of the Router4OLV2 family (csrc/stream_v2.hip): the key set of the cross-frame decoder of ONE
+ * refinement stage for B streams, one launch.  V2 runs the decoder on every frame: on the stream's memory window from frame
+ * min_frames (= cfg.save_freq) after its reset on, on the frame's OWN tokens before (Router4OLV2.py:320-325).  The decision is
+ * cursor[b] >= min_frames (and cursor[b] > 0: an empty memory is never a key set), cursor as phnet_stream_window published it.
+ * local, tgt [B][N][E]; pos [N][E]; window [B][M][E] and window_valid u8 [B][M] = one stage of phnet_stream_window's output;
+ * tgt = local + pos (written where phnet_stream_push reads it); keys [B][Kmax][E], keys_valid u8 [B][Kmax], Kmax >= max(N, M):
+ * rows 0..M-1 = the window with its validity, or rows 0..N-1 = tgt, all valid; the rest zero / invalid.  E % 4 == 0. ---- */
+int phnet_stream_keys(const float* local, const float* pos, const float* window, const uint8_t* window_valid,
+                      const int32_t* cursor, float* tgt, float* keys, uint8_t* keys_valid, int32_t B, int32_t N, int32_t M,
+                      int32_t Kmax, int32_t E, int32_t min_frames, void* stream);
+
 /* ---- Router4OLV2 model family (what testOLV3.py imports; inference only - its training path cannot run as shipped) ----
  * phnet_gate_v2_fwd: AdaptiveRouter4LaneV2.forward (libs/models/Router.py:83-132) in one launch: Conv1d(k3, pad 1, no bias)
  *   + BatchNorm1d + ReLU, Conv1d(k1) + BatchNorm1d + ReLU, Flatten, Linear(C2*P -> P), mean over the P outputs, sigmoid.

@@ -871,6 +871,43 @@ def stream_select(attn, has_memory, feat):
     return feat
 
 
+def stream_keys(local, pos, window, window_valid, cursor, min_frames: int, tgt=None, out=None):
+    """Key set of the Router4OLV2 cross-frame decoder for one stage of B streams (csrc/stream_v2.hip): local [B,N,E], pos [N,E],
+    window [B,M,E] / window_valid bool [B,M] (one stage of stream_window's output), cursor int32 [B] ->
+    (tgt = local + pos [B,N,E], keys [B,Kmax,E], keys_valid bool [B,Kmax]), Kmax = max(N, M).  A stream with
+    0 < cursor >= min_frames gets its window (then zero / invalid rows), the others their own tgt rows, valid (then zero /
+    invalid).  tgt / out = (keys, keys_valid): caller-provided buffers.  One launch."""
+    _req(local, name="local"); _req(pos, name="pos"); _req(window, name="window"); _req(cursor, torch.int32, "cursor")
+    if local.dim() != 3 or window.dim() != 3:
+        raise ValueError("stream_keys: local [B,N,E] and window [B,M,E] expected")
+    b, n, e = local.shape
+    m = window.shape[1]
+    if (tuple(pos.shape) != (n, e) or window.shape[0] != b or window.shape[2] != e or window_valid.dtype != torch.bool
+            or tuple(window_valid.shape) != (b, m) or not window_valid.is_contiguous() or window_valid.device != local.device
+            or cursor.numel() != b or int(min_frames) < 0):
+        raise ValueError(f"stream_keys: local {tuple(local.shape)} vs pos {tuple(pos.shape)} / window {tuple(window.shape)} / "
+                         f"window_valid {tuple(window_valid.shape)} / cursor {tuple(cursor.shape)}, min_frames {min_frames}")
+    kmax = max(n, m)
+    if tgt is None:
+        tgt = torch.empty_like(local)
+    else:
+        _req(tgt, name="tgt out")
+        if tgt.shape != local.shape:
+            raise ValueError("stream_keys: tgt must be [B,N,E] like local")
+    if out is None:
+        keys = torch.empty((b, kmax, e), dtype=torch.float32, device=local.device)
+        valid = torch.empty((b, kmax), dtype=torch.bool, device=local.device)
+    else:
+        keys, valid = out
+        _req(keys, name="keys out")
+        if (keys.dim() != 3 or keys.shape[0] != b or keys.shape[1] < kmax or keys.shape[2] != e or valid.dtype != torch.bool
+                or not valid.is_contiguous() or valid.device != local.device or tuple(valid.shape) != tuple(keys.shape[:2])):
+            raise ValueError("stream_keys: out = (keys [B,Kmax,E] f32, keys_valid bool [B,Kmax]) with Kmax >= max(N, M)")
+    check(lib().phnet_stream_keys(_ptr(local), _ptr(pos), _ptr(window), _ptr(window_valid), _ptr(cursor), _ptr(tgt), _ptr(keys),
+                                  _ptr(valid), b, n, m, keys.shape[1], e, int(min_frames), _stream()), "phnet_stream_keys")
+    return tgt, keys, valid
+
+
 def gate_tail_fwd(h, w, b):
     _req(h, name="h"); _req(w, name="w"); _req(b, name="b")
     n, k = h.shape

@@ -19,6 +19,9 @@ What differs from the V1 family (libs/models/Router4OL.py) and how it is run:
     frame is ONE token per stage - the mean over all 240 anchors.  Reproduced as is (`faithful_memory = True`); the
     evidently intended behaviour (kept lanes' tokens + mean of the rest, as in Router4OL.py:563-584) is one flag away.
 The whole clip runs without a host synchronisation (fused device-side decode + NMS), one device->host copy at the end.
+Three ways in: `infer_device` (one clip, head frame by frame), `infer_clips_device` (B clips, frame t of all clips through the
+head together: `RouterV2.forward_clips`) and `open_stream` (one frame per step for B live videos, memory and frame count on the
+device: phnet_amd/stream.py LaneStreamV2, csrc/stream_v2.hip).
 """
 import math
 
@@ -227,6 +230,59 @@ class RouterV2(nn.Module):
                                                 getattr(self, f"sample_x_indexs_{stage + 1}"))
         return {"predictions_lists": out_a, "seg": None, "flow": None, "predictions_sec": out_b}, attn_feats, gates
 
+    def forward_clips(self, x, last_cuts=None, stage0=None, stream=None, gate_rows=None):
+        """Twin of forward() for the SAME frame index of B independent clips / B live streams: x = the three pyramid levels
+        [B,h,w,C_l]; stage0 = stage_front results [B,...] of stage 0; gate_rows (optional) = [S,B*N] buffer for the gate scores.
+        Every head kernel sees B*N rows; attention stays inside each clip (decoder batch = B).
+        Without `stream`: last_cuts = None / empty (no memory yet: every clip attends to its own tokens) or the list over
+        remembered frames of per-stage (tokens [B,L+1,E], valid [B,L+1]).
+        With `stream` (phnet_amd.stream.StreamState with key buffers): the key set of every stream comes from
+        hip_ops.stream_keys - its memory window from frame cfg.save_freq after its reset on, its own tokens before - and the
+        tokens are written into stream.feat[stage] for the push that follows the decode.
+        Returns (output dict with [B,N,6+S] entries, per-stage tokens [B,N,E], gates [B,N,1]).
+        A twin of forward(), not its body: forward() must keep its results bit for bit, and routing a single frame through here
+        changes its launches (2-D decoder inputs with batch=, expanded priors, other GEMM row plans), which is only known to
+        agree within the batch-shape bound of tests/test_stream_v2_gpu.py, not in bits.  As with DetNetV2.forward / forward_clips."""
+        if self.training:
+            raise NotImplementedError(_INFERENCE_ONLY)
+        levels = list(x)[::-1]
+        B, N = levels[0].shape[0], self.num_priors
+        priors = self.priors.unsqueeze(0).expand(B, -1, -1)
+        on_map = self.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous()
+        pro_feat = self.pro_embedding.weight.detach().unsqueeze(0).expand(B, -1, -1)
+        pos = self.PositionEmbedding.pos_table
+        E = pos.shape[1]
+        out_a, out_b, attn_feats, gates = [], [], [], []
+        for stage in range(self.refine_layers):
+            if stage == 0 and stage0 is not None:
+                fr = stage0
+            else:
+                fr = self.stage_front(levels[stage], stage, priors, on_map, pro_feat, None if gate_rows is None else gate_rows[stage])
+            local = fr["local"]
+            # the own-token key set is unmasked here (valid = None) and all-valid from stream_keys: the attention kernel skips
+            # masked keys and deals the others in order, so an all-true mask takes the unmasked path's arithmetic (held by the
+            # frames before save_freq of "stream == clip" in tests/test_stream_v2_gpu.py)
+            valid = None
+            if stream is not None:
+                attn, mem, valid = K.stream_keys(local.contiguous(), pos, stream.window[stage], stream.window_valid[stage],
+                                                 stream.cursor, self.cfg.save_freq, tgt=stream.feat[stage],
+                                                 out=(stream.keys, stream.keys_valid))
+            else:
+                attn = local + pos                                                   # content + table [B,N,E] (:266-269)
+                mem = attn
+                if last_cuts:
+                    mem = torch.cat([c[stage][0] for c in last_cuts], dim=1)         # [B,M,E]
+                    valid = torch.cat([c[stage][1] for c in last_cuts], dim=1)       # [B,M]
+            feat = self.transformer_Dec(tgt=attn.reshape(B * N, E), memory=mem.reshape(-1, E),
+                                        memory_key_valid=None if valid is None else valid.reshape(-1), batch=B)
+            pred_b, lines_b = self._branch(feat.reshape(B, N, E), priors, True)
+            pro_feat = local
+            out_a.append(fr["pred_a"]); out_b.append(pred_b); attn_feats.append(attn); gates.append(fr["gate"])
+            if stage != self.refine_layers - 1:
+                priors, on_map = K.blend_priors(fr["gate"].contiguous(), fr["lines_a"].contiguous(), lines_b.contiguous(),
+                                                getattr(self, f"sample_x_indexs_{stage + 1}"))
+        return {"predictions_lists": out_a, "seg": None, "flow": None, "predictions_sec": out_b}, attn_feats, gates
+
     # ---- decode (the V1 code: Router4OLV2.py:363-448 repeats Router4OL.py:394-479) -----------------------------------
     predictions_to_pred = DetNetV2.predictions_to_pred
     decode_device = DetNetV2.decode_device
@@ -284,6 +340,43 @@ class RouterOL(nn.Module):
             if t >= self.save_freq_max:
                 last_cuts.pop(0)
         return torch.stack(rows), torch.stack(nums), torch.stack(anchors), dict(frames=aux, gates=gate_rows)
+
+    @torch.no_grad()
+    def infer_clips_device(self, frames: torch.Tensor):
+        """Eval forward of B clips at once, frames [B,T,3,H,W]: the per-frame chain is serial only INSIDE a clip, so frame t of
+        all clips runs through the lane head together (`RouterV2.forward_clips`: B*N rows per kernel, decoder batch = B); stage 0
+        of all T*B frames is one batch.  The memory FIFO stays on the host side of the loop as in `infer_device`.  No host
+        synchronisation (hipGraph-capturable).  Returns (kept_rows [B,T,max_lanes,6+S], num [B,T], anchors [B,T,max_lanes])."""
+        det = self.router
+        B, T = frames.shape[:2]
+        N = det.num_priors
+        feats = self.backbone(frames.transpose(0, 1).reshape(T * B, *frames.shape[2:]))      # frame-major: [t*B + b]
+        n0 = T * B
+        gate_rows = torch.empty((T, det.refine_layers, B * N), dtype=torch.float32, device=frames.device)
+        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(n0, -1, -1).contiguous(),
+                                 det.priors_on_featmap.unsqueeze(0).expand(n0, -1, -1).contiguous(),
+                                 det.pro_embedding.weight.detach().unsqueeze(0).expand(n0, -1, -1))
+        gate_rows[:, 0] = front0["gate"].view(T, B * N)
+        last_cuts, rows, nums, anchors = [], [], [], []
+        for t in range(T):
+            cur = tuple(f[t * B:(t + 1) * B] for f in feats)
+            mem = None if t < self.save_freq else last_cuts
+            outputs, cur_cut, _ = det.forward_clips(cur, mem, {k: v[t * B:(t + 1) * B] for k, v in front0.items()},
+                                                    gate_rows=gate_rows[t])
+            lines = K.route_lines(gate_rows[t], outputs["predictions_lists"][-1].reshape(B * N, -1).contiguous(),
+                                  outputs["predictions_sec"][-1].reshape(B * N, -1).contiguous(), hard=True)      # [B*N,6+S]
+            dec = det.decode_device(lines.view(B, N, -1))                                     # batched over the B clips
+            rows.append(dec["kept_rows"]); nums.append(dec["num"]); anchors.append(dec["anchors"])
+            last_cuts.append(self._memory(cur_cut, dec["anchors_sorted"]))
+            if t >= self.save_freq_max:
+                last_cuts.pop(0)
+        return torch.stack(rows, dim=1), torch.stack(nums, dim=1), torch.stack(anchors, dim=1)
+
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None):
+        """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
+        (phnet_amd.stream.LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame."""
+        from phnet_amd.stream import LaneStreamV2
+        return LaneStreamV2(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw)
 
     def lanes_from_device(self, kept_rows: torch.Tensor, nums: torch.Tensor):
         rows, n = kept_rows.cpu(), nums.cpu().tolist()

@@ -12,6 +12,10 @@ this frame for all stages); no `memory_tokens`, no `torch.cat` of the memory, no
     s.reset()                                                # all streams; s.reset(mask) bool[B]: only those (a camera cut)
     rows, num, anchors = s.step(frames)                      # frames f32 [B,3,H,W]; device tensors, no host synchronisation
     lanes = s.lanes(rows, num)                               # list over streams of Lane lists
+
+`LaneStreamV2` is the same for the Router4OLV2 family (what `Router4OLV2.RouterOL.open_stream` returns): there the decoder runs
+for every stream and `stream_keys` (csrc/stream_v2.hip) picks each stream's key set - its memory window or its own tokens - from
+the device-side frame count.
 """
 from typing import List, Optional, Sequence, Tuple
 
@@ -35,9 +39,12 @@ class StreamState:
     """Device state of B streams, allocated once: ring [S,B,W,L+1,E] / ring_valid bool [S,B,W,L+1] (the token ring; frame i of a
     stream lives in slot i % W), n int32 [B] (frames pushed since the stream's reset) and cursor int32 [B] (the copy of n that
     `stream_window` hands to `stream_push`: no launch reads the word it advances); plus the per-frame buffers window
-    [S,B,W*(L+1),E], window_valid bool [S,B,W*(L+1)], has_memory bool [B] and feat [S,B,N,E] (this frame's attn feats)."""
+    [S,B,W*(L+1),E], window_valid bool [S,B,W*(L+1)], has_memory bool [B] and feat [S,B,N,E] (this frame's attn feats).
+    key_sets=True (the Router4OLV2 family) adds keys [B,Kmax,E] / keys_valid bool [B,Kmax], Kmax = max(N, W*(L+1)): the key set
+    of the stage that is being decoded, rewritten by every stage's `stream_keys` launch; and no_anchors int64 [B,L], all -1 (the
+    anchor list `push` takes when a frame leaves only its mean token in the memory)."""
 
-    def __init__(self, stages: int, streams: int, slots: int, max_lanes: int, num_priors: int, width: int, device):
+    def __init__(self, stages: int, streams: int, slots: int, max_lanes: int, num_priors: int, width: int, device, key_sets: bool = False):
         S, B, W, L, N, E = stages, streams, slots, max_lanes, num_priors, width
         if min(S, B, W, L, N, E) < 1 or L >= N:
             raise ValueError("StreamState: positive sizes and max_lanes < num_priors expected")
@@ -50,6 +57,10 @@ class StreamState:
         self.window_valid = torch.zeros((S, B, W * (L + 1)), dtype=torch.bool, device=device)
         self.has_memory = torch.zeros((B,), dtype=torch.bool, device=device)
         self.feat = torch.zeros((S, B, N, E), **f32)
+        if key_sets:                                              # Router4OLV2: the padded key set of one stage (hip_ops.stream_keys)
+            self.keys = torch.zeros((B, max(N, W * (L + 1)), E), **f32)
+            self.keys_valid = torch.zeros((B, max(N, W * (L + 1))), dtype=torch.bool, device=device)
+            self.no_anchors = torch.full((B, L), -1, dtype=torch.int64, device=device)   # push list of the mean-token-only memory
 
     def load_window(self):
         K.stream_window(self.ring, self.ring_valid, self.n, self.cursor, out=(self.window, self.window_valid, self.has_memory))
@@ -78,15 +89,14 @@ class LaneStream:
                  raw=None, warmup: int = 2):
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
-        det = model.detNet
+        det = self._head(model)
         if frame_hw is None:
             frame_hw = (det.img_h, det.img_w)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("LaneStream: the model must be on the GPU; phnet_amd has no CPU path")
         self.model, self.streams, self.reset_every, self.raw = model.eval(), int(streams), reset_every, raw
-        self.state = StreamState(det.refine_layers, self.streams, model.save_freq_max, det.cfg.max_lanes, det.num_priors,
-                                 det.transformer_Dec.layers[0].self_attn.embed_dim, dev)
+        self.state = self._new_state(det, dev)
         if raw is not None:
             if (raw.out_h, raw.out_w) != tuple(frame_hw):
                 raise ValueError(f"raw= resizes to {raw.out_h}x{raw.out_w}, frame_hw is {tuple(frame_hw)}")
@@ -108,6 +118,14 @@ class LaneStream:
                 self.out = self._body(self.frames)
             torch.cuda.synchronize()
         self.reset()                                              # the warm-up frames are forgotten
+
+    @staticmethod
+    def _head(model):
+        return model.detNet
+
+    def _new_state(self, det, dev) -> StreamState:
+        return StreamState(det.refine_layers, self.streams, self.model.save_freq_max, det.cfg.max_lanes, det.num_priors,
+                           det.transformer_Dec.layers[0].self_attn.embed_dim, dev)
 
     @torch.no_grad()
     def _body(self, frames: torch.Tensor):
@@ -158,3 +176,42 @@ class LaneStream:
     def lanes(self, kept_rows: torch.Tensor, num: torch.Tensor) -> Sequence[list]:
         """Device -> host copy of one step's result, then the host-side Lane construction: a list over streams of Lane lists."""
         return self.model.lanes_from_device(kept_rows, num)["lane_lines"]
+
+
+class LaneStreamV2(LaneStream):
+    """LaneStream for the Router4OLV2 family (libs.models.Router4OLV2.RouterOL): same constructor, same contract.  What differs
+    per frame (DESIGN.md "Streaming path", V2 rules): the cross-frame decoder runs for EVERY stream, on a padded key set that
+    `hip_ops.stream_keys` builds per stage - the stream's memory window from frame `cfg.save_freq` after its reset on, the
+    frame's own tokens before - decided on the device from the frame count `stream_window` published; routing is hard
+    (`route_lines`) over gates laid out [S, B*N]; and with `model.faithful_memory` the pushed memory entry is the one mean token
+    of `saveMemory4Test` as shipped (an all -1 anchor list), otherwise the kept lanes' tokens + the mean of the rest (with
+    graph=True the flag is read once, when the step is captured).  `gate_rows` [S, B*N] holds the gate scores the last step routed
+    with (with graph=True the graph's static buffer, rewritten by the next step)."""
+
+    @staticmethod
+    def _head(model):
+        return model.router
+
+    def _new_state(self, det, dev) -> StreamState:
+        return StreamState(det.refine_layers, self.streams, self.model.save_freq_max, det.cfg.max_lanes, det.num_priors,
+                           det.reg_hidden_dim, dev, key_sets=True)
+
+    @torch.no_grad()
+    def _body(self, frames: torch.Tensor):
+        """Router4OLV2.RouterOL.infer_clips_device's loop body for T = 1 on the B streams, keys and memory on the device."""
+        model, det, st = self.model, self.model.router, self.state
+        B, N = self.streams, det.num_priors
+        x = frames if self.raw is None else self.raw(frames)
+        feats = model.backbone(x)
+        gate_rows = torch.empty((det.refine_layers, B * N), dtype=torch.float32, device=x.device)
+        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                 det.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                 det.pro_embedding.weight.detach().unsqueeze(0).expand(B, -1, -1), gate_rows[0])
+        st.load_window()
+        outputs, _, _ = det.forward_clips(feats, None, front0, stream=st, gate_rows=gate_rows)
+        lines = K.route_lines(gate_rows, outputs["predictions_lists"][-1].reshape(B * N, -1).contiguous(),
+                              outputs["predictions_sec"][-1].reshape(B * N, -1).contiguous(), hard=True)
+        dec = det.decode_device(lines.view(B, N, -1))
+        st.push(st.no_anchors if model.faithful_memory else dec["anchors_sorted"])
+        self.gate_rows = gate_rows                                 # [S, B*N] of the last step (graph=True: the graph's static buffer)
+        return dec["kept_rows"], dec["num"], dec["anchors"]

@@ -41,7 +41,7 @@ def spread_scores_(model, std: float = 0.5, seed: int = 11) -> None:
     For inference benchmarks: redraw the class heads of both branches with a visible spread, so that about half of the 240
     anchors of every frame pass conf_threshold (K ~ 120 candidates into the NMS, max_lanes keepers, positives in memory)."""
     g = torch.Generator().manual_seed(seed)
-    det = model.detNet
+    det = model.detNet if hasattr(model, "detNet") else model.router          # Router4OL / Router4OLV2 family
     with torch.no_grad():
         for lin in (det.cls_layers, det.cls_layers_sec):
             lin.weight.copy_(torch.randn(lin.weight.shape, generator=g).to(lin.weight) * std)
