@@ -52,6 +52,19 @@ int phnet_lane_decode(const float* lines, int64_t frames, int32_t N, int32_t n_o
                       float nms_thresh, int64_t top_k, float img_w, uint8_t* keep_mask, int64_t* num,
                       int64_t* keep_c, int64_t* anchors, int64_t* anchors_sorted, float* kept_rows, void* stream);
 
+/* ---- lane polylines: replaces DetNetV2.predictions_to_pred (libs/models/Router4OL.py:394-435) up to the points of each lane,
+ * one launch for all frames, no host synchronisation (csrc/lane_points.hip; the rules are listed there and in DESIGN.md
+ * "Streaming path").  kept_rows [F][L][6+S] and num i64 [F] as phnet_lane_decode writes them (column 5 in strips); prior_ys [S].
+ * points [F][L][S][2]: the (x, y) pairs of the frame's lanes, normalised, in the host's order (descending offset index); lanes
+ *   are PACKED - lane k is the k-th lane the host list would hold; the unused tail of a lane and unused lanes are zeros.
+ * count i32 [F][L]: points of packed lane k (0 = unused);  lanes_num i32 [F]: kept slots that yield more than one point;
+ * slot i32 [F][L]: the kept_rows slot packed lane k came from (-1 = unused) - conf, start_y, start_x are columns 1, 2, 3 of it.
+ * Values are copied, never computed: bit-identical to the host's float64 points after widening.  A row whose start_y or
+ * length is NaN or +-inf (the host code raises on it) is not a lane.  Every output element is written on every call.
+ * Limits: 1 <= F < 2^31, 1 <= L <= 64, 2 <= S <= 256. */
+int phnet_lane_points(const float* kept_rows, const int64_t* num, const float* prior_ys, int64_t F, int32_t L, int32_t S,
+                      float* points, int32_t* count, int32_t* lanes_num, int32_t* slot, void* stream);
+
 /* ---- lane-anchor ROI pooling: replaces F.grid_sample(..., align_corners=True) + permutes
  * (libs/models/Router4OL.py:132-150, 269-272) and its backward (ATen grid_sampler_2d_backward).
  * fmap [B][h][w][64]; xs [B][N][P] = priors_on_featmap (un-flipped); ys [P] = prior_feat_ys; out [B][N][P][64]. */

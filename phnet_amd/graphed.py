@@ -133,12 +133,18 @@ class GraphedInference:
     """Eval forward of a fixed-length clip (backbone + lane head + fused decode/NMS for every frame) captured in one
     hipGraph; `__call__` copies the frames in, replays, and returns the device-resident (kept_rows, num, anchors).
     frames [T,3,H,W]: one clip (RouterOL.infer_device); frames [B,T,3,H,W]: B clips per replay with the lane head
-    batched across the clips (RouterOL.infer_clips_device)."""
+    batched across the clips (RouterOL.infer_clips_device).  polylines=True captures the lane-points launch as well
+    (RouterOL.infer_points_device): `__call__` returns the same triple and `polylines` holds the device-resident points / count /
+    lanes_num / slot of the last replay (static graph buffers, like the triple)."""
 
-    def __init__(self, model: torch.nn.Module, frames: torch.Tensor, warmup: int = 2):
+    def __init__(self, model: torch.nn.Module, frames: torch.Tensor, warmup: int = 2, polylines: bool = False):
         self.model = model.eval()
         self.frames = frames.clone()
-        infer = model.infer_clips_device if frames.dim() == 5 else model.infer_device
+        self.polylines = None
+        if polylines:
+            infer = model.infer_points_device
+        else:
+            infer = model.infer_clips_device if frames.dim() == 5 else model.infer_device
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
@@ -149,6 +155,8 @@ class GraphedInference:
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.out = infer(self.frames)
+        if polylines:
+            self.out, self.polylines = self.out[:3], self.out[3]
         torch.cuda.synchronize()
 
     def __call__(self, frames: torch.Tensor):

@@ -1028,6 +1028,37 @@ def lane_decode(lines, conf_thresh: float, nms_thresh: float, top_k: int, img_w:
     return out if batched else {k: v[0] for k, v in out.items()}
 
 
+LANE_POINTS_MAX_LANES, LANE_POINTS_MAX_OFFSETS = 64, 256      # limits of phnet_lane_points (csrc/lane_points.hip)
+
+
+def lane_points(kept_rows, num, prior_ys, out=None):
+    """kept_rows [L,6+S] or [F,L,6+S] and num i64 [] / [F] as lane_decode returns them, prior_ys [S] -> dict(points f32 [..,L,S,2],
+    count i32 [..,L], lanes_num i32 [..], slot i32 [..,L]): the (x, y) polylines of DetNetV2.predictions_to_pred, packed per
+    frame, in one launch; everything stays on the device (no sync).  out: such a dict (of the [F,...] shapes) to write into."""
+    _req(kept_rows, name="kept_rows"); _req(num, torch.int64, "num"); _req(prior_ys, name="prior_ys")
+    if kept_rows.dim() not in (2, 3):
+        raise ValueError("lane_points: kept_rows [L,6+S] or [F,L,6+S] expected")
+    batched = kept_rows.dim() == 3
+    f = kept_rows.shape[0] if batched else 1
+    l, s = kept_rows.shape[-2], kept_rows.shape[-1] - 6
+    if num.numel() != f or prior_ys.numel() != s or num.device != kept_rows.device or prior_ys.device != kept_rows.device:
+        raise ValueError(f"lane_points: kept_rows {tuple(kept_rows.shape)} vs num {tuple(num.shape)} / prior_ys {tuple(prior_ys.shape)}")
+    dev = kept_rows.device
+    shapes = dict(points=((f, l, s, 2), torch.float32), count=((f, l), torch.int32), lanes_num=((f,), torch.int32),
+                  slot=((f, l), torch.int32))
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    else:
+        for k, (shape, dt) in shapes.items():
+            _req(out[k], dt, k + " out")
+            if tuple(out[k].shape) != shape or out[k].device != dev:
+                raise ValueError(f"lane_points: out[{k!r}] must be {shape}, got {tuple(out[k].shape)}")
+        out = {k: out[k] for k in shapes}
+    check(lib().phnet_lane_points(_ptr(kept_rows), _ptr(num), _ptr(prior_ys), f, l, s, _ptr(out["points"]), _ptr(out["count"]),
+                                  _ptr(out["lanes_num"]), _ptr(out["slot"]), _stream()), "phnet_lane_points")
+    return out if batched else {k: v[0] for k, v in out.items()}
+
+
 # ------------------------------------------------------------------------------------------------ Router4OLV2 family (inference)
 def gate_v2_fwd(x_cp, w1, s1, t1, w2, s2, t2, wl, bl, out: Optional[torch.Tensor] = None):
     """x_cp [M,C,P] -> sigmoid(mean(Linear(flatten(conv-bn-relu x2)))) [M]  (csrc/v2head.hip)."""

@@ -354,6 +354,12 @@ class DetNetV2(nn.Module):
         tp = self.cfg.test_parameters
         return K.lane_decode(lines.contiguous(), tp.conf_threshold, tp.nms_thres, self.cfg.max_lanes, self.img_w)
 
+    def points_device(self, dec, out=None):
+        """decode_device's result (or any dict with kept_rows [..,max_lanes,6+S] and num [..]) -> the device-resident form of
+        predictions_to_pred (hip_ops.lane_points): dict(points [..,max_lanes,S,2], count, lanes_num, slot), one launch, no sync."""
+        from phnet_amd import hip_ops as K
+        return K.lane_points(dec["kept_rows"].contiguous(), dec["num"].contiguous(), self.prior_ys.contiguous(), out=out)
+
     def get_lanes(self, output, org_size=None, crop_size=0, as_lanes=True):
         """output [B,N,6+S] blended lines -> (decoded per batch item, keep_inds, keep) as in Router4OL.py:437-479."""
         decoded, keep_inds, keep = [], None, []
@@ -381,7 +387,15 @@ class DetNetV2(nn.Module):
         return decoded, keep_inds, keep
 
 
-BRANCH_B_SITES = 1 << 10      # dropout site numbering of branch B inside DropoutStream.items (functional.py)
+def _points_of(det, kept_rows: torch.Tensor, nums: torch.Tensor) -> dict:
+    """Polylines of kept_rows [..,max_lanes,6+S] / nums [..] with any leading dimensions (frames of a clip, clips x frames): ONE
+    hip_ops.lane_points launch over all of them, the outputs shaped like the inputs.  Shared by both model families."""
+    lead = tuple(nums.shape)
+    out = det.points_device({"kept_rows": kept_rows.reshape(-1, *kept_rows.shape[-2:]), "num": nums.reshape(-1)})
+    return {k: v.view(*lead, *v.shape[1:]) for k, v in out.items()}
+
+
+BRANCH_B_SITES = 1 << 10     # dropout site numbering of branch B inside DropoutStream.items (functional.py)
 
 
 class _Stacked(list):
@@ -774,11 +788,25 @@ class RouterOL(nn.Module):
         rows, n = kept_rows.cpu(), nums.cpu().tolist()
         return {"lane_lines": [self.detNet.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
 
-    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None):
+    def infer_points_device(self, frames: torch.Tensor):
+        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
+        returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
+        more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
+        rows, nums, anchors = self.infer_device(frames) if frames.dim() == 4 else self.infer_clips_device(frames)
+        return rows, nums, anchors, _points_of(self.detNet, rows, nums)
+
+    def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
+        """One device->host copy of the polylines and their rows, then numpy slicing (phnet_amd.polylines.to_host): a list over
+        frames (nested like the leading dimensions) of lists of Polyline.  The fast counterpart of lanes_from_device."""
+        from phnet_amd import polylines as P
+        return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
+
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
         """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
-        (phnet_amd.stream.LaneStream: reset / step / lanes); one captured hipGraph serves every frame."""
+        (phnet_amd.stream.LaneStream: reset / step / lanes); one captured hipGraph serves every frame.  polylines=True: the step
+        also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
         from phnet_amd.stream import LaneStream
-        return LaneStream(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw)
+        return LaneStream(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw, polylines=polylines)
 
     def forward(self, inputs: dict):
         frame, lanes = inputs.values()

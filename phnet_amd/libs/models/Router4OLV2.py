@@ -36,7 +36,7 @@ from ..utils.lane import Lane
 from .fpnV2 import FPN
 from .resnet import ResNetWrapper
 from .Router import AdaptiveRouter4LaneV2
-from .Router4OL import DetNetV2, LinearModule
+from .Router4OL import DetNetV2, LinearModule, _points_of
 from .utils.dynamic_head import DynamicConvV2
 from .utils.transformer import TransformerDecoder, TransformerDecoderLayer
 
@@ -286,6 +286,7 @@ class RouterV2(nn.Module):
     # ---- decode (the V1 code: Router4OLV2.py:363-448 repeats Router4OL.py:394-479) -----------------------------------
     predictions_to_pred = DetNetV2.predictions_to_pred
     decode_device = DetNetV2.decode_device
+    points_device = DetNetV2.points_device
     get_lanes = DetNetV2.get_lanes
 
 
@@ -372,11 +373,27 @@ class RouterOL(nn.Module):
                 last_cuts.pop(0)
         return torch.stack(rows, dim=1), torch.stack(nums, dim=1), torch.stack(anchors, dim=1)
 
-    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None):
+    @torch.no_grad()
+    def infer_points_device(self, frames: torch.Tensor):
+        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
+        returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
+        more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
+        rows, nums, anchors = self.infer_device(frames)[:3] if frames.dim() == 4 else self.infer_clips_device(frames)
+        return rows, nums, anchors, _points_of(self.router, rows, nums)
+
+    def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
+        """One device->host copy of the polylines and their rows, then numpy slicing (phnet_amd.polylines.to_host): a list over
+        frames (nested like the leading dimensions) of lists of Polyline.  The fast counterpart of lanes_from_device."""
+        from phnet_amd import polylines as P
+        return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
+
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
         """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
-        (phnet_amd.stream.LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame."""
+        (phnet_amd.stream.LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.  polylines=True: the
+        step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
         from phnet_amd.stream import LaneStreamV2
-        return LaneStreamV2(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw)
+        return LaneStreamV2(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw,
+                            polylines=polylines)
 
     def lanes_from_device(self, kept_rows: torch.Tensor, nums: torch.Tensor):
         rows, n = kept_rows.cpu(), nums.cpu().tolist()

@@ -13,6 +13,11 @@ this frame for all stages); no `memory_tokens`, no `torch.cat` of the memory, no
     rows, num, anchors = s.step(frames)                      # frames f32 [B,3,H,W]; device tensors, no host synchronisation
     lanes = s.lanes(rows, num)                               # list over streams of Lane lists
 
+With `open_stream(..., polylines=True)` the step ends with one more launch (csrc/lane_points.hip) that leaves the lanes' (x, y)
+points on the device in `s.polylines` (points, count, lanes_num, slot); `s.lanes_fast()` copies them to the host once and slices:
+
+    lines = s.lanes_fast()                                   # list over streams of phnet_amd.polylines.Polyline lists
+
 `LaneStreamV2` is the same for the Router4OLV2 family (what `Router4OLV2.RouterOL.open_stream` returns): there the decoder runs
 for every stream and `stream_keys` (csrc/stream_v2.hip) picks each stream's key set - its memory window or its own tokens - from
 the device-side frame count.
@@ -83,10 +88,14 @@ class LaneStream:
     chunking of the reference's testOL.py:104-117).  raw: a ClipPreprocessor - `step` then takes camera-format uint8 frames
     [B,src_h,src_w,3] and the crop / resize / normalise launch is part of the step (and of the captured graph).
 
-    With graph=True the returned tensors are the graph's static outputs: the next `step` overwrites them."""
+    polylines=True: the last launch of the step (inside the captured graph) is `hip_ops.lane_points`; `polylines` then holds its
+    four device tensors for the last step (points [B,max_lanes,S,2], count, lanes_num, slot) and `lanes_fast()` reads them.  What
+    `step` returns does not change.
+
+    With graph=True the returned tensors (and `polylines`) are the graph's static outputs: the next `step` overwrites them."""
 
     def __init__(self, model, streams: int = 1, frame_hw: Tuple[int, int] = None, graph: bool = True, reset_every: Optional[int] = None,
-                 raw=None, warmup: int = 2):
+                 raw=None, warmup: int = 2, polylines: bool = False):
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
         det = self._head(model)
@@ -96,6 +105,7 @@ class LaneStream:
         if dev.type != "cuda":
             raise RuntimeError("LaneStream: the model must be on the GPU; phnet_amd has no CPU path")
         self.model, self.streams, self.reset_every, self.raw = model.eval(), int(streams), reset_every, raw
+        self.want_polylines, self.polylines = bool(polylines), None
         self.state = self._new_state(det, dev)
         if raw is not None:
             if (raw.out_h, raw.out_w) != tuple(frame_hw):
@@ -145,6 +155,12 @@ class LaneStream:
         dec = det.decode_device(lines)
         st.push(dec["anchors_sorted"])
         model._begin_clip()
+        return self._result(det, dec)
+
+    def _result(self, det, dec):
+        """What `step` returns; with polylines=True the lane points of this frame first, as the last launch of the step."""
+        if self.want_polylines:
+            self.polylines, self._rows = det.points_device(dec), dec["kept_rows"]      # the rows `slot` points into
         return dec["kept_rows"], dec["num"], dec["anchors"]
 
     def reset(self, mask=None):
@@ -176,6 +192,14 @@ class LaneStream:
     def lanes(self, kept_rows: torch.Tensor, num: torch.Tensor) -> Sequence[list]:
         """Device -> host copy of one step's result, then the host-side Lane construction: a list over streams of Lane lists."""
         return self.model.lanes_from_device(kept_rows, num)["lane_lines"]
+
+    def lanes_fast(self) -> Sequence[list]:
+        """The lanes of the last step from the device-side polylines: one device -> host copy, numpy slicing, no splines
+        (phnet_amd.polylines.to_host).  A list over streams of Polyline lists, lane for lane the points of `lanes`."""
+        if self.polylines is None:
+            raise RuntimeError("lanes_fast: open the stream with polylines=True and run a step first")
+        from . import polylines as P
+        return P.to_host(self.polylines["points"], self.polylines["count"], self.polylines["lanes_num"], self.polylines["slot"], self._rows)
 
 
 class LaneStreamV2(LaneStream):
@@ -214,4 +238,4 @@ class LaneStreamV2(LaneStream):
         dec = det.decode_device(lines.view(B, N, -1))
         st.push(st.no_anchors if model.faithful_memory else dec["anchors_sorted"])
         self.gate_rows = gate_rows                                 # [S, B*N] of the last step (graph=True: the graph's static buffer)
-        return dec["kept_rows"], dec["num"], dec["anchors"]
+        return self._result(det, dec)
