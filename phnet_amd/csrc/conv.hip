@@ -1494,6 +1494,10 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
     float* dst = splits > 1 ? workspace : out;
     dim3 grid((unsigned)p.tiles, 1, (unsigned)splits);
     const int ksteps = (K + p.bkt - 1) / p.bkt;
+    // ceil, so the last split can come out short or - with the 64-deep tile, where ksteps < splits * (splits - 1) happens (240 x
+    // 1856 -> 2880: 29 steps, 7 splits of 5) - EMPTY: its workgroups skip the K loop and write zeros to their slice of the
+    // partial sums (tests/gemm_cases.py "empty_split").  With 16-deep tiles plan_conv keeps >= 256 of K = 16 steps per split
+    // and splits <= 8, so ksteps >= 16 * splits > splits * (splits - 1): no empty split there
     g.k_per_split = ((ksteps + splits - 1) / splits) * p.bkt;
 #define PHNET_LAUNCH_CONV___(BM_, BN_, BKT_, UNI_, MMA_, PF_)                                                           \
     do {                                                                                                                \
@@ -1535,7 +1539,10 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
     } while (0)
     if (p.taps3) {
         const int units = 3 * (g.Ci / 16);
-        g.k_per_split = (units + splits - 1) / splits;                   // in units for this kernel
+        // in units for this kernel.  The last split can be short (15 units over 2 splits), never empty: K / splits >= 256
+        // (plan_conv) is units >= 5.34 * splits, and units < splits * (splits - 1) would then need splits > 6 - at 7 and 8
+        // splits the only unit counts in range (39; 45, 48, 51, 54) leave the last split 3, 3, 6, 2 and 5 units
+        g.k_per_split = (units + splits - 1) / splits;
         constexpr size_t lds_ = 2 * 3 * T3_AROWS * KContigPlanes<64, 16>::PITCH +
                                 2 * (size_t)(DGRAD ? KStridedPlanes<64, 16>::BYTES : KContigPlanes<64, 16>::BYTES) + 3 * 512;
         hipLaunchKernelGGL((conv3x3s1_kernel<DGRAD>), grid, dim3(THREADS), lds_, st,
@@ -1758,6 +1765,9 @@ static WgradPick pick_wgrad(const WgradShape& g, bool has_dbias, bool has_ws, ui
     // Linear / 1x1 layers over many rows with >= 64 tiles of 128 x 128: the producer / consumer kernel (csrc/wgrad1s.hip)
     if (tn.wgrad1s && tn.mma_mode == 3 && linear && (Co & 127) == 0 && (Ci & 127) == 0 && P >= 256 &&
         (long)(Co / 128) * (Ci / 128) >= 64 && P * (long)max(Ci, Co) * 4 < 0x7fffffffL) {
+        // at most 256 / 64 = 4 splits of >= 128 rows = 8 steps each: steps >= 8 * splits > splits * (splits - 1), so the last
+        // split can be short but never empty.  (The other families can get an empty one - 391 pixels, 6 splits: 25 steps of 16
+        // in splits of 5 - and their kernels then write zeros: tests/gemm_cases.py "empty_split".)
         const long tiles = (long)(Co / 128) * (Ci / 128);
         return {WgradFamily::ManyRowsPC, 128, phnet_wgrad1s_kstep(), 3, fit(max((long)1, min((long)(P / 128), (long)256 / tiles)))};
     }

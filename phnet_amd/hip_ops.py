@@ -249,12 +249,14 @@ def conv3p(x: torch.Tensor, packed: torch.Tensor, nn: int, dgrad: bool = False, 
     return (out, (part, nblk)) if stats else out
 
 
-def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: Optional[torch.Tensor] = None):
+def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None):
     _req(dy, name="dy"); _req(w, name="w")
     n = dy.shape[0]
     co, r, s, ci = w.shape
     hi, wi = in_hw
-    dx = torch.empty((n, hi, wi, ci), dtype=torch.float32, device=dy.device)
+    dx = torch.empty((n, hi, wi, ci), dtype=torch.float32, device=dy.device) if out is None else _req(out, name="out")
+    assert dx.shape == (n, hi, wi, ci)
     need = 8 * n * hi * wi * ci * 4 if n * hi * wi * ci < (1 << 23) else 0
     ws = workspace(need, dy.device) if need else None
     m, k = n * hi * wi, r * s * co

@@ -132,7 +132,7 @@ CONV_CASES = [
     (1, 10, 25, 512, 512, 3, 1, 1),        # split-K path (few tiles, long K)
     (2, 33, 47, 4, 64, 7, 2, 3),           # stem geometry (3 channels padded to 4), ragged sizes
     (3, 9, 13, 128, 64, 1, 1, 0),
-    (1, 80, 200, 64, 64, 3, 1, 1),         # 128x64 tile path
+    (1, 80, 200, 64, 64, 3, 1, 1),         # 250 tiles: conv3x3s1_kernel at 2 splits, wgrad3s / conv_wgrad3x3 at 85 (128-row tiles: tests/gemm_cases.py)
     (240, 1, 1, 1024, 8192, 1, 1, 0),      # hyper-net linear
     (240, 1, 1, 4608, 1024, 1, 1, 0),      # long-K linear -> split-K
     (240, 1, 1, 64, 36, 1, 1, 0),          # ragged Co (36 offsets)
@@ -263,8 +263,11 @@ def test_conv_fwd_dgrad_wgrad_bf16x3(ops, bf16x3, case):
     close(dw, 2 * w.grad.permute(0, 2, 3, 1), 2e-5)
 
 
-@pytest.mark.parametrize("case", [(2, 16, 20, 64, 64), (3, 5, 17, 64, 128), (4, 2, 5, 512, 512), (1, 1, 70, 64, 64), (5, 20, 50, 256, 64),
-                                  (1, 10, 25, 512, 512), (4, 3, 23, 128, 64), (3, 8, 20, 128, 128), (2, 2, 2, 64, 64), (1, 40, 100, 64, 192)])
+CONV3P_CASES = [(2, 16, 20, 64, 64), (3, 5, 17, 64, 128), (4, 2, 5, 512, 512), (1, 1, 70, 64, 64), (5, 20, 50, 256, 64),
+                (1, 10, 25, 512, 512), (4, 3, 23, 128, 64), (3, 8, 20, 128, 128), (2, 2, 2, 64, 64), (1, 40, 100, 64, 192)]      # N, Hi, Wi, Ci, Co
+
+
+@pytest.mark.parametrize("case", CONV3P_CASES)
 def test_packed_weight_3x3_kernel_vs_fp64(ops, bf16x3, case):
     """conv3p_kernel (csrc/conv3p.hip: 3x3 / stride 1 / pad 1 on weights packed into bf16 planes in MFMA fragment order), forward
     and data gradient: image rows narrower / wider than the 128-pixel block, blocks that span image rows and frames, one- and
@@ -305,7 +308,10 @@ def test_packed_weight_3x3_kernel_vs_fp64(ops, bf16x3, case):
     close(ops.conv3p(gyd, pd, Ci, dgrad=True), ops.conv2d_dgrad(gyd, wd, (Hi, Wi), 1, 1).double().cpu(), 2e-5)
 
 
-@pytest.mark.parametrize("case", [(1200, 1024, 1024), (257, 1152, 1024), (300, 1024, 1152), (1200, 2048, 512)])
+WGRAD1S_CASES = [(1200, 1024, 1024), (257, 1152, 1024), (300, 1024, 1152), (1200, 2048, 512)]      # P, Ci, Co
+
+
+@pytest.mark.parametrize("case", WGRAD1S_CASES)
 def test_many_row_linear_weight_gradient_kernel_vs_fp64(ops, bf16x3, case):
     """wgrad1s_kernel (csrc/wgrad1s.hip: 128 x 128 tiles, 8 consumer + 4 producer waves) - the weight and bias gradient of a Linear
     layer over many rows: ragged row counts (a last step of one row), overwrite and accumulate, with and without the bias
@@ -336,8 +342,11 @@ def test_many_row_linear_weight_gradient_kernel_vs_fp64(ops, bf16x3, case):
     close(dw_nb, dw_generic, 1e-5)
 
 
-@pytest.mark.parametrize("case", [(2, 16, 20, 64, 64), (3, 5, 17, 64, 128), (2, 7, 16, 128, 64), (1, 1, 70, 64, 64), (5, 20, 50, 256, 64),
-                                  (1, 10, 25, 512, 512), (4, 3, 23, 64, 64), (4, 1, 20, 64, 64), (3, 2, 16, 64, 64)])
+WGRAD3_CASES = [(2, 16, 20, 64, 64), (3, 5, 17, 64, 128), (2, 7, 16, 128, 64), (1, 1, 70, 64, 64), (5, 20, 50, 256, 64),
+                (1, 10, 25, 512, 512), (4, 3, 23, 64, 64), (4, 1, 20, 64, 64), (3, 2, 16, 64, 64)]      # N, Hi, Wi, Ci, Co
+
+
+@pytest.mark.parametrize("case", WGRAD3_CASES)
 def test_wgrad_three_taps_kernel_vs_fp64(ops, bf16x3, case):
     """conv_wgrad3x3_kernel (3x3 / stride 1 / pad 1, the three taps of a filter row from one staged pixel block): image rows
     narrower / wider than the 16-pixel block, blocks that span image rows and frames, one-row images (every row is the top and
@@ -385,8 +394,11 @@ def test_wgrad_three_taps_kernel_vs_fp64(ops, bf16x3, case):
             assert lib().phnet_tune_reset() == 0
 
 
-@pytest.mark.parametrize("case", [(2, 16, 20, 64, 64), (3, 5, 17, 16, 36), (2, 7, 16, 48, 64), (1, 1, 70, 32, 128), (5, 20, 50, 256, 64),
-                                  (1, 10, 25, 512, 512), (4, 3, 2, 64, 64), (1, 80, 200, 64, 64)])
+TAPS3_CASES = [(2, 16, 20, 64, 64), (3, 5, 17, 16, 36), (2, 7, 16, 48, 64), (1, 1, 70, 32, 128), (5, 20, 50, 256, 64),
+               (1, 10, 25, 512, 512), (4, 3, 2, 64, 64), (1, 80, 200, 64, 64)]      # N, Hi, Wi, Ci, Co
+
+
+@pytest.mark.parametrize("case", TAPS3_CASES)
 def test_conv3x3_three_taps_forward_and_dgrad_vs_fp64(ops, bf16x3, case):
     """conv3x3s1_kernel (3x3 / stride 1 / pad 1: a staged 66-pixel block serves the three taps of a filter row): blocks that span
     image rows and frames, one-row and two-pixel-wide images, pixel counts that are no multiple of the tile, channel counts of 1-3
@@ -965,7 +977,10 @@ def test_dropout_add_layernorm_fused(ops, L):
     close(dx2[kept], (dres2 / (1 - p))[kept], 1e-5)
 
 
-@pytest.mark.parametrize("M,K,N", [(240, 128, 384), (240, 192, 44), (240, 256, 128), (37, 64, 64), (256, 2304, 64), (240, 2304, 576)])
+LINEAR_BWD_CASES = [(240, 128, 384), (240, 192, 44), (240, 256, 128), (37, 64, 64), (256, 2304, 64), (240, 2304, 576)]      # M, K, N
+
+
+@pytest.mark.parametrize("M,K,N", LINEAR_BWD_CASES)
 def test_linear_backward_fused_launch(ops, M, K, N):
     """dx, dW (accumulated) and dbias of a few-rows Linear layer from ONE launch vs fp64 torch."""
     assert ops.linear_bwd_fusable(M, K, N)
