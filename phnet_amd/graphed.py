@@ -19,6 +19,18 @@ import torch
 from .trunk import weights_changed
 
 
+def warm_up(fn: Callable[[], object], warmup: int):
+    """What precedes every capture here: fn() `warmup` times on a side stream (lazy allocations, first launches and autograd's
+    per-stream state happen off the stream that will capture), then the side stream is joined and the device synchronised."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+
+
 def data_parallel_step(model, arena, reducer, optimizer, frames, lanes, loss_divisor: float, stage_done=None):
     """One data-parallel training step, eagerly or under hipGraph capture:
     zero | trunk forward (staged, SyncBatchNorm exchanges inside) + lane head + loss | head backward | bucket 0 out |
@@ -64,13 +76,7 @@ class GraphedTrainStep:
             from . import parallel, rccl
             if parallel.active() and dist.get_backend() == "nccl" and rccl.installed() is None:
                 rccl.install()                              # collective (every rank builds its step at the same point); eager
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        warm_up(self._step, warmup)
         self.graph = torch.cuda.CUDAGraph()
         self.graph_opt = None
         if arena is None:
@@ -145,13 +151,8 @@ class GraphedInference:
             infer = model.infer_points_device
         else:
             infer = model.infer_clips_device if frames.dim() == 5 else model.infer_device
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup):
-                infer(self.frames)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        with torch.no_grad():
+            warm_up(lambda: infer(self.frames), warmup)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.out = infer(self.frames)

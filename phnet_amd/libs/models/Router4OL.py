@@ -228,10 +228,8 @@ class DetNetV2(nn.Module):
     def stage_back(self, front, stage, priors, memory):
         """Branch B of ONE frame on top of its stage_front results (all [1,...])."""
         gate, local = front["gate"], front["local"]
-        attn = front.get("attn")
-        if attn is None:
-            pos = self.PositionEmbedding.embed.weight.unsqueeze(1)                   # [N,1,C]
-            attn = torch.cat([local.transpose(0, 1), pos], dim=-1)                   # [N,1,2C]
+        pos = self.PositionEmbedding.embed.weight.unsqueeze(1)                       # [N,1,C]
+        attn = torch.cat([local.transpose(0, 1), pos], dim=-1)                       # [N,1,2C]
         pred_b, lines_b = self.forward_second(memory, attn, stage, priors)
         return dict(pred_a=front["pred_a"], lines_a=front["lines_a"], pred_b=pred_b, lines_b=lines_b, attn=attn, gate=gate, local=local)
 
@@ -240,20 +238,24 @@ class DetNetV2(nn.Module):
         memory None | [M,1,2C] | ([M,1,2C], valid bool[M]).  Returns dict(pred_a, lines_a, pred_b, lines_b, attn, gate, local)."""
         return self.stage_back(self.stage_front(fmap, stage, priors, on_map, pro_feat), stage, priors, memory)
 
+    def stage0_front(self, fmap):
+        """stage_front of stage 0 for the B frames of fmap [B,h,w,C] (the frames of a clip, of several clips, or one frame of B
+        streams): they all start from the same learned anchors and embeddings.  self.priors must be current (training callers
+        run generate_priors_from_embeddings first)."""
+        B = fmap.shape[0]
+        return self.stage_front(fmap, 0, self.priors.unsqueeze(0).expand(B, -1, -1),
+                                self.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                self.pro_embedding.weight.unsqueeze(0).expand(B, -1, -1))
+
     def stage0_all_frames(self, fmaps0):
         """Stage 0 of every frame starts from the same learned anchors and embeddings, and only its branch B looks at
         earlier frames - so ROI pooling, routing gate, dynamic head and branch A of stage 0 run ONCE for the whole clip (GEMM rows
         T*N instead of N, a fifth of the launches).  fmaps0 [T,h,w,C] = the stage-0 pyramid level of all frames.
         Returns a list over frames of stage_front dicts ([1,...] views; their gradients meet in one cat)."""
-        T = fmaps0.shape[0]
         if self.training:
             self.priors, self.priors_on_featmap = self.generate_priors_from_embeddings()
-        priors = self.priors.unsqueeze(0).expand(T, -1, -1)
-        on_map = self.priors_on_featmap.unsqueeze(0).expand(T, -1, -1).contiguous()
-        pro = self.pro_embedding.weight.unsqueeze(0).expand(T, -1, -1)
-        front = self.stage_front(fmaps0, 0, priors, on_map, pro)
-        parts = {k: v.split(1, dim=0) for k, v in front.items()}
-        return [{k: parts[k][t] for k in parts} for t in range(T)]
+        parts = {k: v.split(1, dim=0) for k, v in self.stage0_front(fmaps0).items()}
+        return [{k: parts[k][t] for k in parts} for t in range(fmaps0.shape[0])]
 
     def forward(self, x, last_cuts=None, stage0=None):
         """x = (P3, P4, P5) NHWC [1,h,w,C] for ONE frame; last_cuts = list over remembered frames of per-stage tokens;
@@ -354,6 +356,16 @@ class DetNetV2(nn.Module):
         tp = self.cfg.test_parameters
         return K.lane_decode(lines.contiguous(), tp.conf_threshold, tp.nms_thres, self.cfg.max_lanes, self.img_w)
 
+    def blended_lines(self, outputs, gates):
+        """The eval output of a frame (Router4OL.py:538-541): the last stage's lines of branch B and branch A blended by the
+        mean over the stages of the routing gates.  [B,N,6+S]."""
+        d = torch.stack(gates, dim=0).mean(dim=0)
+        return outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
+
+    def decode_frame(self, outputs, gates):
+        """decode_device of the gate-blended lines [B,N,6+S] of one frame index, outputs / gates from forward_clips()."""
+        return self.decode_device(self.blended_lines(outputs, gates))
+
     def points_device(self, dec, out=None):
         """decode_device's result (or any dict with kept_rows [..,max_lanes,6+S] and num [..]) -> the device-resident form of
         predictions_to_pred (hip_ops.lane_points): dict(points [..,max_lanes,S,2], count, lanes_num, slot), one launch, no sync."""
@@ -393,6 +405,39 @@ def _points_of(det, kept_rows: torch.Tensor, nums: torch.Tensor) -> dict:
     lead = tuple(nums.shape)
     out = det.points_device({"kept_rows": kept_rows.reshape(-1, *kept_rows.shape[-2:]), "num": nums.reshape(-1)})
     return {k: v.view(*lead, *v.shape[1:]) for k, v in out.items()}
+
+
+class DeviceResults:
+    """What a RouterOL of either family does with the device-resident results of its infer_device / infer_clips_device: to host
+    lanes, to polylines, and the frame-at-a-time stream.  The model says where its lane head lives (`head`) and which class of
+    phnet_amd.stream serves it (`stream_class`)."""
+    stream_class = "LaneStream"
+
+    def lanes_from_device(self, kept_rows: torch.Tensor, nums: torch.Tensor):
+        """One device->host copy per clip, then the host-side Lane construction (Router4OL.py:394-435)."""
+        rows, n = kept_rows.cpu(), nums.cpu().tolist()
+        return {"lane_lines": [self.head.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
+
+    def infer_points_device(self, frames: torch.Tensor):
+        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
+        returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
+        more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
+        rows, nums, anchors = (self.infer_device(frames) if frames.dim() == 4 else self.infer_clips_device(frames))[:3]
+        return rows, nums, anchors, _points_of(self.head, rows, nums)
+
+    def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
+        """One device->host copy of the polylines and their rows, then numpy slicing (phnet_amd.polylines.to_host): a list over
+        frames (nested like the leading dimensions) of lists of Polyline.  The fast counterpart of lanes_from_device."""
+        from phnet_amd import polylines as P
+        return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
+
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
+        """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
+        (phnet_amd.stream.LaneStream / LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.
+        polylines=True: the step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
+        from phnet_amd import stream
+        return getattr(stream, self.stream_class)(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every,
+                                                  raw=raw, polylines=polylines)
 
 
 BRANCH_B_SITES = 1 << 10     # dropout site numbering of branch B inside DropoutStream.items (functional.py)
@@ -457,7 +502,9 @@ class _BranchBDeferred(torch.autograd.Function):
         return (None, None, None, None, None, None, d_pri0) + tuple(d_tok) + tuple(d_par)
 
 
-class RouterOL(nn.Module):
+class RouterOL(nn.Module, DeviceResults):
+    SCHEDULES = ("stage", "frame")
+
     def __init__(self, cfg, criterion=None):
         super().__init__()
         self.backbone = Encoder(cfg=cfg)
@@ -468,21 +515,28 @@ class RouterOL(nn.Module):
         self.org_size = (cfg.dscfg.org_height, cfg.dscfg.org_width)
         self.sync_free_eval = True      # eval: fused device-side decode, one D2H copy per clip (False: per-frame get_lanes)
         self.batch_stage0 = True        # stage-0 ROI pooling / dynamic head / branch A of all frames in one batch
-        # training schedule of the (frame, stage) grid: "wavefront" (anti-diagonals: branch B of up to 3 pairs as one batch),
-        # "stage" (every stage's frame-independent front batched over the frames, branch B frame by frame) or "frame" (the
-        # reference's loop order)
-        self.schedule = "stage"          # measured at T = 5, ResNet-34 320x800: frame 25.0, stage 22.3, wavefront 22.9 ms per step
+        # training schedule of the (frame, stage) grid: "stage" (every stage's frame-independent front batched over the frames,
+        # branch B frame by frame) or "frame" (the reference's loop order, what the tests compare "stage" against).  Measured at
+        # T = 5, ResNet-34 320x800: frame 25.0, stage 22.3 ms per step; a third, "wavefront" schedule (anti-diagonals of the grid:
+        # branch B of up to 3 pairs as one batch) took 22.9 ms, never won and was dropped
+        self.schedule = "stage"
         # stage-major schedule only: branch B's passes run forward without autograd and their backward runs as ONE batch
         # (_BranchBDeferred); False: every pass is its own autograd sub-graph (same arithmetic, same dropout masks)
         self.defer_branch_b = True
 
     @property
-    def stage_major(self):
-        return self.schedule != "frame"
+    def head(self):
+        return self.detNet
 
-    @stage_major.setter
-    def stage_major(self, on: bool):
-        self.schedule = "stage" if on else "frame"
+    @property
+    def schedule(self) -> str:
+        return self._schedule
+
+    @schedule.setter
+    def schedule(self, name: str):
+        if name not in self.SCHEDULES:
+            raise ValueError(f"RouterOL.schedule: one of {self.SCHEDULES} expected, got {name!r}")
+        self._schedule = name
 
     def _begin_clip(self):
         det = self.detNet
@@ -508,9 +562,8 @@ class RouterOL(nn.Module):
         for t in range(frame.shape[0]):
             cur = tuple(f[t:t + 1] for f in feats)
             outputs, cur_cut, gates = self.detNet(cur, last_cuts, None if stage0 is None else stage0[t])
-            d = torch.stack(gates, dim=0).mean(dim=0)
-            lines = outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
-            dec = self.detNet.decode_device(lines[0])
+            # the single frame of forward() as [N,6+S]: results without a leading dimension, stacked over the frames below
+            dec = self.detNet.decode_device(self.detNet.blended_lines(outputs, gates)[0])
             rows.append(dec["kept_rows"]); nums.append(dec["num"]); anchors.append(dec["anchors"])
             last_cuts.append([self._tokens(feat.detach(), dec["anchors_sorted"]) for feat in cur_cut])
             if t >= self.save_freq_max:
@@ -527,17 +580,12 @@ class RouterOL(nn.Module):
         self._begin_clip()
         feats = self.backbone(frames.transpose(0, 1).reshape(T * B, *frames.shape[2:]))      # frame-major: [t*B + b]
         det = self.detNet
-        n0 = feats[-1].shape[0]
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(n0, -1, -1),
-                                 det.priors_on_featmap.unsqueeze(0).expand(n0, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.unsqueeze(0).expand(n0, -1, -1))
+        front0 = det.stage0_front(feats[-1])                                                  # all T*B frames in one batch
         last_cuts, rows, nums, anchors = [], [], [], []
         for t in range(T):
             cur = tuple(f[t * B:(t + 1) * B] for f in feats)
             outputs, cur_cut, gates = det.forward_clips(cur, last_cuts, {k: v[t * B:(t + 1) * B] for k, v in front0.items()})
-            d = torch.stack(gates, dim=0).mean(dim=0)
-            lines = outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
-            dec = det.decode_device(lines)                                                    # batched over the B clips
+            dec = det.decode_frame(outputs, gates)                                            # batched over the B clips
             rows.append(dec["kept_rows"]); nums.append(dec["num"]); anchors.append(dec["anchors"])
             last_cuts.append([K.memory_tokens(feat.detach().contiguous(), dec["anchors_sorted"].contiguous()) for feat in cur_cut])
             if t >= self.save_freq_max:
@@ -558,11 +606,7 @@ class RouterOL(nn.Module):
         feats = self.backbone(frames.transpose(0, 1).reshape(T * B, *frames.shape[2:]))      # frame-major: [t*B + b]
         det = self.detNet
         det.priors, det.priors_on_featmap = det.generate_priors_from_embeddings()
-        n0 = feats[-1].shape[0]
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(n0, -1, -1),
-                                 det.priors_on_featmap.unsqueeze(0).expand(n0, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.unsqueeze(0).expand(n0, -1, -1))
-        front0 = {k: v.split(B, dim=0) for k, v in front0.items()}                           # per frame index: [B,...] (one cat backward)
+        front0 = {k: v.split(B, dim=0) for k, v in det.stage0_front(feats[-1]).items()}      # per frame index: [B,...] (one cat backward)
         levels = [f.split(B, dim=0) for f in feats]
         last_cuts, total_loss = [], 0.0
         for t in range(T):
@@ -614,7 +658,7 @@ class RouterOL(nn.Module):
         return pred
 
     def _clip_loss(self, per_frame, lanes):
-        """Criterion over the frames of a clip whose predictions are all there (stage-major / wavefront schedules): one call when
+        """Criterion over the frames of a clip whose predictions are all there (stage-major schedule): one call when
         the criterion offers `clip_loss` (loss4OLV3: two launches for the clip), else the reference's loop (trainOLV3.py:150-171)."""
         outs = [{"predictions_fir": fr["predictions_fir"], "predictions_sec": fr["predictions_sec"]} for fr in per_frame]
         if hasattr(self.criterion, "clip_loss"):
@@ -644,6 +688,8 @@ class RouterOL(nn.Module):
         feats = self.backbone(frame)                                           # 3 x [T,h,w,C] NHWC
         levels = list(feats)[::-1]
         det.priors, det.priors_on_featmap = det.generate_priors_from_embeddings()
+        # the state the stage loop starts from and hands on; not stage0_front: branch B of stage 0 and _BranchBDeferred (pri0) take
+        # these expanded priors too, and their gradients must meet in this one expand
         priors = det.priors.unsqueeze(0).expand(T, -1, -1)
         on_map = det.priors_on_featmap.unsqueeze(0).expand(T, -1, -1).contiguous()
         pro = det.pro_embedding.weight.unsqueeze(0).expand(T, -1, -1)
@@ -707,107 +753,6 @@ class RouterOL(nn.Module):
                     per_frame[t]["predictions_sec"].append(pb[s_ * T + t])
         return self._clip_loss(per_frame, lanes)
 
-    def train_clip_wavefront(self, frame: torch.Tensor, lanes: torch.Tensor):
-        """Training forward of one clip as a WAVEFRONT over (frame t, stage s).  (t, s) depends on (t, s-1) - its priors are
-        that stage's blend - and on (t' < t, s) - branch B attends to the stage-s tokens of earlier frames; so every pair on
-        an anti-diagonal t + s = d is independent of the others.  Branch B is the launch-bound part of the step (two decoder
-        layers + towers: ~40 forward and ~50 backward launches on 240 rows, 15 times in a row) and uses the SAME transformer
-        and tower weights at every stage (Router4OL.py:86-103): the up to three pairs of a wavefront go through it as ONE
-        batch (the attention kernels treat them as independent clips, their memory windows are fixed-length slices of the
-        per-stage token rings with key masks), i.e. T + 2 serial branch-B passes instead of 3T.  The frame-independent front
-        of stages 1 and 2 (ROI pooling, gate, dynamic head, branch A: per-stage weights) runs per pair; stage 0's for the
-        whole clip at once.  Same arithmetic per (t, s) as the frame-major loop (tests/test_model_gpu.py)."""
-        from phnet_amd import hip_ops as K
-        det = self.detNet
-        T, S, N = frame.shape[0], det.refine_layers, det.num_priors
-        W, L1 = self.save_freq_max, lanes.shape[1] + 1
-        dev = frame.device
-        feats = self.backbone(frame)                                           # 3 x [T,h,w,C] NHWC
-        levels = [lv.split(1, dim=0) for lv in list(feats)[::-1]]              # levels[s][t]: [1,h,w,C]
-        det.priors, det.priors_on_featmap = det.generate_priors_from_embeddings()
-        pos = det.PositionEmbedding.embed.weight.unsqueeze(0)                  # [1,N,C]
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(T, -1, -1),
-                                 det.priors_on_featmap.unsqueeze(0).expand(T, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.unsqueeze(0).expand(T, -1, -1))
-        front0["attn"] = torch.cat([front0["local"], pos.expand(T, -1, -1)], dim=-1)
-        front0 = {k: v.split(1, dim=0) for k, v in front0.items()}
-        pri0 = det.priors.unsqueeze(0)
-        E = 2 * det.fc_hidden_dim
-        # per-stage token rings with W leading slots that are never valid: frame t's window is ALWAYS ring[t : t + W]
-        ring = [torch.zeros((W + T, L1, E), dtype=torch.float32, device=dev) for _ in range(S)]
-        ring_valid = [torch.zeros((W + T, L1), dtype=torch.bool, device=dev) for _ in range(S)]
-        nxt = {}                                                               # (t, s) -> (priors, on_map, pro) for its front
-        per_frame = [{"predictions_fir": [None] * S, "predictions_sec": [None] * S, "gates": [None] * S} for _ in range(T)]
-        for d in range(T + S - 1):
-            pairs = [(t, d - t) for t in range(T) if 0 <= d - t < S]
-            fronts, priors = [], []
-            for t, s in pairs:
-                if s == 0:
-                    fr, pri = {k: v[t] for k, v in front0.items()}, pri0
-                else:
-                    pri, on_map, pro = nxt.pop((t, s))
-                    fr = det.stage_front(levels[s][t], s, pri, on_map, pro)
-                    fr["attn"] = torch.cat([fr["local"], pos], dim=-1)
-                fronts.append(fr); priors.append(pri)
-            # ---- branch B of the whole wavefront: pairs with earlier frames go through the decoder as one batch ----
-            with_mem = [i for i, (t, s) in enumerate(pairs) if t > 0]
-            feat = [fr["attn"][0] for fr in fronts]                            # [N,E] each
-            if with_mem:
-                tgt = torch.cat([feat[i] for i in with_mem], dim=0) if len(with_mem) > 1 else feat[with_mem[0]]
-                mem = torch.cat([ring[pairs[i][1]][pairs[i][0]:pairs[i][0] + W].view(-1, E) for i in with_mem], dim=0)
-                valid = torch.cat([ring_valid[pairs[i][1]][pairs[i][0]:pairs[i][0] + W].view(-1) for i in with_mem], dim=0)
-                dec = det.transformer_Dec(tgt=tgt, memory=mem, memory_key_valid=valid, batch=len(with_mem))
-                for j, i in enumerate(with_mem):
-                    feat[i] = dec[j * N:(j + 1) * N]
-            feat_all = torch.stack(feat, dim=0) if len(feat) > 1 else feat[0].unsqueeze(0)          # [k,N,E]
-            pri_all = torch.cat(priors, dim=0) if len(priors) > 1 else priors[0]
-            pred_b, lines_b = det._branch(feat_all, pri_all, True)                                   # [k,N,6+S]
-            pb = pred_b.split(1, dim=0) if len(pairs) > 1 else [pred_b]
-            with torch.no_grad():
-                for i, (t, s) in enumerate(pairs):
-                    _, rows_sorted, _ = K.lane_assign(pb[i][0].detach().contiguous(), lanes[t].contiguous(), det.img_w, det.img_h)
-                    K.memory_tokens(fronts[i]["attn"][0].detach().contiguous(), rows_sorted.contiguous(),
-                                    out=(ring[s][W + t], ring_valid[s][W + t]))
-                todo = [i for i, (t, s) in enumerate(pairs) if s + 1 < S]
-                if todo:
-                    gate = torch.cat([fronts[i]["gate"].detach() for i in todo], dim=0)
-                    la = torch.cat([fronts[i]["lines_a"].detach() for i in todo], dim=0)
-                    lb = lines_b.detach() if len(todo) == len(pairs) else torch.cat([lines_b[i:i + 1].detach() for i in todo], dim=0)
-                    pri_n, map_n = K.blend_priors(gate.contiguous(), la.contiguous(), lb.contiguous(), det.sample_x_indexs)
-                    for j, i in enumerate(todo):
-                        t, s = pairs[i]
-                        nxt[(t, s + 1)] = (pri_n[j:j + 1], map_n[j:j + 1], fronts[i]["local"].detach())
-            for i, (t, s) in enumerate(pairs):
-                per_frame[t]["predictions_fir"][s] = fronts[i]["pred_a"]
-                per_frame[t]["predictions_sec"][s] = pb[i]
-                per_frame[t]["gates"][s] = fronts[i]["gate"]
-        return self._clip_loss(per_frame, lanes)
-
-    def lanes_from_device(self, kept_rows: torch.Tensor, nums: torch.Tensor):
-        """One device->host copy per clip, then the host-side Lane construction (Router4OL.py:394-435)."""
-        rows, n = kept_rows.cpu(), nums.cpu().tolist()
-        return {"lane_lines": [self.detNet.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
-
-    def infer_points_device(self, frames: torch.Tensor):
-        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
-        returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
-        more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
-        rows, nums, anchors = self.infer_device(frames) if frames.dim() == 4 else self.infer_clips_device(frames)
-        return rows, nums, anchors, _points_of(self.detNet, rows, nums)
-
-    def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
-        """One device->host copy of the polylines and their rows, then numpy slicing (phnet_amd.polylines.to_host): a list over
-        frames (nested like the leading dimensions) of lists of Polyline.  The fast counterpart of lanes_from_device."""
-        from phnet_amd import polylines as P
-        return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
-
-    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
-        """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
-        (phnet_amd.stream.LaneStream: reset / step / lanes); one captured hipGraph serves every frame.  polylines=True: the step
-        also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
-        from phnet_amd.stream import LaneStream
-        return LaneStream(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw, polylines=polylines)
-
     def forward(self, inputs: dict):
         frame, lanes = inputs.values()
         if not frame.is_cuda:
@@ -825,8 +770,8 @@ class RouterOL(nn.Module):
         self._begin_clip()
         if self.training:
             PF.DropoutStream.begin_step(frame.device)                          # fresh dropout masks for this clip's fwd + bwd
-            if self.schedule != "frame" and self.batch_stage0:
-                loss = (self.train_clip_wavefront if self.schedule == "wavefront" else self.train_clip_stage_major)(frame, lanes)
+            if self.schedule == "stage" and self.batch_stage0:
+                loss = self.train_clip_stage_major(frame, lanes)
                 self._begin_clip()
                 return loss
         feats = self.backbone(frame)                                           # 3 x [T,h,w,C] NHWC
@@ -842,8 +787,7 @@ class RouterOL(nn.Module):
                 matched, frame_loss = self.criterion(outputs, lanes[t:t + 1], gates)
                 total_loss = total_loss + frame_loss
             else:
-                d = torch.stack(gates, dim=0).mean(dim=0)
-                lines = outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
+                lines = self.detNet.blended_lines(outputs, gates)
                 lane_lines, keep_inds, keep = self.detNet.get_lanes(lines, self.org_size, self.crop_size)
                 clip_outputs["lane_lines"].append(lane_lines[0])
             with torch.no_grad():

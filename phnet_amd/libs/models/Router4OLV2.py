@@ -36,7 +36,7 @@ from ..utils.lane import Lane
 from .fpnV2 import FPN
 from .resnet import ResNetWrapper
 from .Router import AdaptiveRouter4LaneV2
-from .Router4OL import DetNetV2, LinearModule, _points_of
+from .Router4OL import DetNetV2, DeviceResults, LinearModule
 from .utils.dynamic_head import DynamicConvV2
 from .utils.transformer import TransformerDecoder, TransformerDecoderLayer
 
@@ -201,6 +201,14 @@ class RouterV2(nn.Module):
         pred_a, lines_a = self.forward_first(local, priors)
         return dict(gate=gate, local=local, pred_a=pred_a, lines_a=lines_a)
 
+    def stage0_front(self, fmap, gate_out=None):
+        """stage_front of stage 0 for the B frames of fmap [B,h,w,C_0] (the frames of a clip, of several clips, or one frame of B
+        streams): they all start from the same learned anchors and embeddings.  gate_out (optional): [B*N] buffer for the gates."""
+        B = fmap.shape[0]
+        return self.stage_front(fmap, 0, self.priors.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                self.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
+                                self.pro_embedding.weight.detach().unsqueeze(0).expand(B, -1, -1), gate_out)
+
     def forward(self, x, last_cuts=None, stage0=None, gate_rows=None):
         """x = the three pyramid levels (fine -> coarse, NHWC [1,h,w,C_l]) of ONE frame; last_cuts = None (no memory yet: the
         decoder attends to the frame's own tokens) or a list over remembered frames of per-stage (tokens, valid).
@@ -289,8 +297,22 @@ class RouterV2(nn.Module):
     points_device = DetNetV2.points_device
     get_lanes = DetNetV2.get_lanes
 
+    def decode_frame(self, outputs, gate_rows, B=None):
+        """decode_device of the HARD-routed last-stage lines of one frame index: gate_rows [S,B*N] (the scores of all stages),
+        outputs from forward() / forward_clips().  B clips or streams: decoded as [B,N,6+S]; B = None: the single frame of
+        forward(), decoded as [N,6+S] - results without a leading dimension (infer_device stacks them over the frames).
+        The routed lines ride along as `lines` [B*N,6+S]."""
+        width = outputs["predictions_sec"][-1].shape[-1]
+        lines = K.route_lines(gate_rows, outputs["predictions_lists"][-1].reshape(-1, width).contiguous(),
+                              outputs["predictions_sec"][-1].reshape(-1, width).contiguous(), hard=True)
+        dec = self.decode_device(lines if B is None else lines.view(B, self.num_priors, -1))
+        dec["lines"] = lines
+        return dec
 
-class RouterOL(nn.Module):
+
+class RouterOL(nn.Module, DeviceResults):
+    stream_class = "LaneStreamV2"
+
     def __init__(self, cfg, criterion=None):
         super().__init__()
         if cfg.backbone == "revcol":
@@ -304,6 +326,10 @@ class RouterOL(nn.Module):
         self.org_size = (cfg.dscfg.org_height, cfg.dscfg.org_width)
         self.faithful_memory = True     # True: saveMemory4Test as shipped (memory = mean token only); False: kept lanes + mean of the rest
         self.batch_stage0 = True        # stage-0 pooling / gate / dynamic head / branch A of all frames in one batch
+
+    @property
+    def head(self):
+        return self.router
 
     def _memory(self, attn_feats, anchors_sorted):
         """Per stage (tokens [L+1,1,E], valid [L+1]): the positives' tokens (none when faithful_memory) + the mean of the rest."""
@@ -322,9 +348,7 @@ class RouterOL(nn.Module):
         gate_rows = torch.empty((T, det.refine_layers, N), dtype=torch.float32, device=frame.device)
         stage0 = None
         if self.batch_stage0:
-            front = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(T, -1, -1).contiguous(),
-                                    det.priors_on_featmap.unsqueeze(0).expand(T, -1, -1).contiguous(),
-                                    det.pro_embedding.weight.detach().unsqueeze(0).expand(T, -1, -1))
+            front = det.stage0_front(feats[-1])
             gate_rows[:, 0] = front["gate"].view(T, N)
             stage0 = [{k: v[t:t + 1] for k, v in front.items()} for t in range(T)]
         last_cuts, rows, nums, anchors, aux = [], [], [], [], []
@@ -332,11 +356,9 @@ class RouterOL(nn.Module):
             cur = tuple(f[t:t + 1] for f in feats)
             mem = None if t < self.save_freq else last_cuts
             outputs, cur_cut, gates = det(cur, mem, None if stage0 is None else stage0[t], gate_rows[t])
-            lines = K.route_lines(gate_rows[t], outputs["predictions_lists"][-1][0].contiguous(),
-                                  outputs["predictions_sec"][-1][0].contiguous(), hard=True)          # [N,6+S]
-            dec = det.decode_device(lines)
+            dec = det.decode_frame(outputs, gate_rows[t])
             rows.append(dec["kept_rows"]); nums.append(dec["num"]); anchors.append(dec["anchors"])
-            aux.append(dict(lines=lines, outputs=outputs, keep_mask=dec["keep_mask"], keep_c=dec["keep_c"]))
+            aux.append(dict(lines=dec["lines"], outputs=outputs, keep_mask=dec["keep_mask"], keep_c=dec["keep_c"]))
             last_cuts.append(self._memory([c.detach() for c in cur_cut], dec["anchors_sorted"]))
             if t >= self.save_freq_max:
                 last_cuts.pop(0)
@@ -352,11 +374,8 @@ class RouterOL(nn.Module):
         B, T = frames.shape[:2]
         N = det.num_priors
         feats = self.backbone(frames.transpose(0, 1).reshape(T * B, *frames.shape[2:]))      # frame-major: [t*B + b]
-        n0 = T * B
         gate_rows = torch.empty((T, det.refine_layers, B * N), dtype=torch.float32, device=frames.device)
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(n0, -1, -1).contiguous(),
-                                 det.priors_on_featmap.unsqueeze(0).expand(n0, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.detach().unsqueeze(0).expand(n0, -1, -1))
+        front0 = det.stage0_front(feats[-1])                                                  # all T*B frames in one batch
         gate_rows[:, 0] = front0["gate"].view(T, B * N)
         last_cuts, rows, nums, anchors = [], [], [], []
         for t in range(T):
@@ -364,9 +383,7 @@ class RouterOL(nn.Module):
             mem = None if t < self.save_freq else last_cuts
             outputs, cur_cut, _ = det.forward_clips(cur, mem, {k: v[t * B:(t + 1) * B] for k, v in front0.items()},
                                                     gate_rows=gate_rows[t])
-            lines = K.route_lines(gate_rows[t], outputs["predictions_lists"][-1].reshape(B * N, -1).contiguous(),
-                                  outputs["predictions_sec"][-1].reshape(B * N, -1).contiguous(), hard=True)      # [B*N,6+S]
-            dec = det.decode_device(lines.view(B, N, -1))                                     # batched over the B clips
+            dec = det.decode_frame(outputs, gate_rows[t], B)                                  # batched over the B clips
             rows.append(dec["kept_rows"]); nums.append(dec["num"]); anchors.append(dec["anchors"])
             last_cuts.append(self._memory(cur_cut, dec["anchors_sorted"]))
             if t >= self.save_freq_max:
@@ -375,29 +392,9 @@ class RouterOL(nn.Module):
 
     @torch.no_grad()
     def infer_points_device(self, frames: torch.Tensor):
-        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
-        returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
-        more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
-        rows, nums, anchors = self.infer_device(frames)[:3] if frames.dim() == 4 else self.infer_clips_device(frames)
-        return rows, nums, anchors, _points_of(self.router, rows, nums)
-
-    def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
-        """One device->host copy of the polylines and their rows, then numpy slicing (phnet_amd.polylines.to_host): a list over
-        frames (nested like the leading dimensions) of lists of Polyline.  The fast counterpart of lanes_from_device."""
-        from phnet_amd import polylines as P
-        return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
-
-    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
-        """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
-        (phnet_amd.stream.LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.  polylines=True: the
-        step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
-        from phnet_amd.stream import LaneStreamV2
-        return LaneStreamV2(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every, raw=raw,
-                            polylines=polylines)
-
-    def lanes_from_device(self, kept_rows: torch.Tensor, nums: torch.Tensor):
-        rows, n = kept_rows.cpu(), nums.cpu().tolist()
-        return {"lane_lines": [self.router.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
+        """DeviceResults.infer_points_device under no_grad whoever calls, like infer_clips_device here (this family has no training
+        path).  Not on the shared method: the V1 infer_* methods follow the caller's grad mode, which picks their branch kernels."""
+        return super().infer_points_device(frames)
 
     def forward(self, inputs: dict):
         frame, lanes = inputs.values()

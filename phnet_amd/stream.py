@@ -27,6 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import hip_ops as K
+from .graphed import warm_up
 
 
 def window_order(n: int, W: int) -> List[int]:
@@ -98,7 +99,7 @@ class LaneStream:
                  raw=None, warmup: int = 2, polylines: bool = False):
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
-        det = self._head(model)
+        det = model.head
         if frame_hw is None:
             frame_hw = (det.img_h, det.img_w)
         dev = next(model.parameters()).device
@@ -116,22 +117,12 @@ class LaneStream:
         self.frame_index = 0                                      # host-side count of steps, for reset_every only
         self.graph, self.out = None, None
         if graph:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._body(self.frames)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            warm_up(lambda: self._body(self.frames), warmup)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.out = self._body(self.frames)
             torch.cuda.synchronize()
         self.reset()                                              # the warm-up frames are forgotten
-
-    @staticmethod
-    def _head(model):
-        return model.detNet
 
     def _new_state(self, det, dev) -> StreamState:
         return StreamState(det.refine_layers, self.streams, self.model.save_freq_max, det.cfg.max_lanes, det.num_priors,
@@ -140,19 +131,14 @@ class LaneStream:
     @torch.no_grad()
     def _body(self, frames: torch.Tensor):
         """infer_clips_device's loop body for T = 1 on the B streams, the memory taken from / pushed to the device ring."""
-        model, det, st = self.model, self.model.detNet, self.state
-        B = self.streams
+        model, det, st = self.model, self.model.head, self.state
         model._begin_clip()
         x = frames if self.raw is None else self.raw(frames)
         feats = model.backbone(x)
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(B, -1, -1),
-                                 det.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.unsqueeze(0).expand(B, -1, -1))
+        front0 = det.stage0_front(feats[-1])
         st.load_window()
         outputs, _, gates = det.forward_clips(feats, None, front0, stream=st)
-        d = torch.stack(gates, dim=0).mean(dim=0)
-        lines = outputs["predictions_sec"][-1] * d + outputs["predictions_fir"][-1] * (1 - d)
-        dec = det.decode_device(lines)
+        dec = det.decode_frame(outputs, gates)
         st.push(dec["anchors_sorted"])
         model._begin_clip()
         return self._result(det, dec)
@@ -212,10 +198,6 @@ class LaneStreamV2(LaneStream):
     graph=True the flag is read once, when the step is captured).  `gate_rows` [S, B*N] holds the gate scores the last step routed
     with (with graph=True the graph's static buffer, rewritten by the next step)."""
 
-    @staticmethod
-    def _head(model):
-        return model.router
-
     def _new_state(self, det, dev) -> StreamState:
         return StreamState(det.refine_layers, self.streams, self.model.save_freq_max, det.cfg.max_lanes, det.num_priors,
                            det.reg_hidden_dim, dev, key_sets=True)
@@ -223,19 +205,15 @@ class LaneStreamV2(LaneStream):
     @torch.no_grad()
     def _body(self, frames: torch.Tensor):
         """Router4OLV2.RouterOL.infer_clips_device's loop body for T = 1 on the B streams, keys and memory on the device."""
-        model, det, st = self.model, self.model.router, self.state
+        model, det, st = self.model, self.model.head, self.state
         B, N = self.streams, det.num_priors
         x = frames if self.raw is None else self.raw(frames)
         feats = model.backbone(x)
         gate_rows = torch.empty((det.refine_layers, B * N), dtype=torch.float32, device=x.device)
-        front0 = det.stage_front(feats[-1], 0, det.priors.unsqueeze(0).expand(B, -1, -1).contiguous(),
-                                 det.priors_on_featmap.unsqueeze(0).expand(B, -1, -1).contiguous(),
-                                 det.pro_embedding.weight.detach().unsqueeze(0).expand(B, -1, -1), gate_rows[0])
+        front0 = det.stage0_front(feats[-1], gate_rows[0])
         st.load_window()
         outputs, _, _ = det.forward_clips(feats, None, front0, stream=st, gate_rows=gate_rows)
-        lines = K.route_lines(gate_rows, outputs["predictions_lists"][-1].reshape(B * N, -1).contiguous(),
-                              outputs["predictions_sec"][-1].reshape(B * N, -1).contiguous(), hard=True)
-        dec = det.decode_device(lines.view(B, N, -1))
+        dec = det.decode_frame(outputs, gate_rows, B)
         st.push(st.no_anchors if model.faithful_memory else dec["anchors_sorted"])
         self.gate_rows = gate_rows                                 # [S, B*N] of the last step (graph=True: the graph's static buffer)
         return self._result(det, dec)

@@ -83,6 +83,20 @@ def test_no_cpu_fallback():
     assert "oracle" not in src
 
 
+def test_training_schedule_rejects_unknown_names():
+    """RouterOL.schedule takes "stage" (default) and "frame"; a dropped schedule or a typo raises at the assignment instead of
+    silently running the stage-major schedule."""
+    from phnet_amd.libs.models.Router4OL import RouterOL
+    model = RouterOL(make_cfg(img_h=64, img_w=160, arch="resnet18"), None)
+    assert model.schedule == "stage"
+    for bad in ("wavefront", "stages"):
+        with pytest.raises(ValueError):
+            model.schedule = bad
+    assert model.schedule == "stage"
+    model.schedule = "frame"
+    assert model.schedule == "frame"
+
+
 def test_host_side_lane_decode_matches_oracle():
     from phnet_amd.libs.models.Router4OL import RouterOL
     g = O.Geometry(img_h=64, img_w=160, arch="resnet18")

@@ -502,11 +502,11 @@ def test_dropout_masks_advance_with_each_graph_replay_and_match_between_forward_
         assert float(loss_with_pinned_masks(snap + 8)) != float(loss_with_pinned_masks(snap))
 
 
-@pytest.mark.parametrize("schedule", ["stage", "stage_direct", "wavefront"])
+@pytest.mark.parametrize("schedule", ["stage", "stage_direct"])
 def test_batched_training_schedules_equal_frame_major(schedule):
     """RouterOL.schedule: "stage" (every stage's frame-independent part batched over the clip's frames, branch B + assignment
-    + memory tokens walking the frames) and "wavefront" (the pairs of an anti-diagonal t + s = d share ONE batched branch-B
-    pass, memory windows as masked fixed-length ring slices) against the reference-shaped frame-major loop: same per-frame
+    + memory tokens walking the frames), with branch B's backward as one batch and ("stage_direct") as one autograd sub-graph
+    per pass, against the reference-shaped frame-major loop: same per-frame
     losses and matched anchors (the stand-alone assignment that feeds the memory == the criterion's own), gradients to
     re-association noise.  11 frames: three more than the memory depth, so the token window slides."""
     g = O.Geometry(img_h=64, img_w=160, arch="resnet18")
