@@ -65,6 +65,35 @@ int phnet_lane_decode(const float* lines, int64_t frames, int32_t N, int32_t n_o
 int phnet_lane_points(const float* kept_rows, const int64_t* num, const float* prior_ys, int64_t F, int32_t L, int32_t S,
                       float* points, int32_t* count, int32_t* lanes_num, int32_t* slot, void* stream);
 
+/* ---- lane identities: a stable id per lane across the frames of a stream (csrc/lane_track.hip; no counterpart in the reference,
+ * which leaves an unordered lane set per frame).  One launch for B streams, one wavefront per stream walking its T frames in order
+ * (T = 1: the streaming step; T > 1: a clip), no host synchronisation.  kept_rows [B][T][L][6+S] and num i64 [B][T] as
+ * phnet_lane_decode writes them.  State, read and written by the call (caller-owned, one set per B streams): trk_id i32 [B][M]
+ * (0 = free slot), trk_missed i32 [B][M], trk_hits i32 [B][M], trk_ext i32 [B][M][2] (start, end), trk_x [B][M][S] (the xs of the
+ * last matched row: copied, never computed), next_id i32 [B] (starts at 1; < 1 is read as 1).  Out, every element written on every
+ * call: track_id i32 [B][T][L] (-1 = not trackable), track_hits i32 [B][T][L] (0 = not trackable).
+ * Per frame, in this order (a slot is live when its id != 0):
+ *   1. start = clamp(rint(double(r[2]) * (S-1)), 0, S-1), end = min(start + rint(double(r[5])) - 1, S-1) (the extent rule of
+ *      phnet_lane_points).  Row d is trackable iff d < clamp(num, 0, L), r[2] and r[5] are finite and end >= start; any other row
+ *      gets track_id -1, hits 0 and never touches the state.
+ *   2. (trackable row d, live slot k): lo = max(starts), hi = min(ends), skipped if hi < lo; sum = f32 accumulation of
+ *      |row_x[i] - slot_x[i]| for i = lo..hi ascending, each term a < b ? b - a : a - b, not contracted; cnt = hi - lo + 1.  The
+ *      pair is a candidate iff sum < thr * (float)cnt (one f32 multiply, strict <; a NaN in the range: not a candidate).
+ *   3. greedy, smallest mean first: (sum_p, cnt_p) before (sum_q, cnt_q) iff double(sum_p) * cnt_q < double(sum_q) * cnt_p (exact,
+ *      no division), ties to the lower d, then the lower k; pairs are taken in that order, skipping rows and slots already taken.
+ *      A match copies the row's xs and extent into the slot, missed = 0, hits += 1; the row gets the slot's id and hits.
+ *   4. every live slot not matched: missed += 1; missed > max_age frees it (id = 0).
+ *   5. every trackable unmatched row, ascending d: the lowest free slot, else the slot with the largest missed among those neither
+ *      matched nor filled in this frame (ties: lowest slot); id = next_id, next_id advances and wraps from 2^31 - 1 to 1;
+ *      hits = 1, missed = 0, the row is copied in.
+ * thr is in the units of kept_rows (xs normalised by img_w - 1).  A reset of a stream is trk_id[b][*] = 0 by the caller; next_id is
+ * kept, so ids never repeat within a stream's state.
+ * Limits (PHNET_ERR_ARG before any launch): 1 <= L <= M <= 64, 2 <= S <= 256, (L + M) * S + 2 * L * M <= 15360 (the LDS staging),
+ * 1 <= T, 1 <= B < 2^31, max_age >= 0, thr finite and > 0, all pointers non-null. */
+int phnet_lane_track(const float* kept_rows, const int64_t* num, int64_t B, int32_t T, int32_t L, int32_t S, int32_t M, float thr,
+                     int32_t max_age, int32_t* trk_id, int32_t* trk_missed, int32_t* trk_hits, int32_t* trk_ext, float* trk_x,
+                     int32_t* next_id, int32_t* track_id, int32_t* track_hits, void* stream);
+
 /* ---- lane-anchor ROI pooling: replaces F.grid_sample(..., align_corners=True) + permutes
  * (libs/models/Router4OL.py:132-150, 269-272) and its backward (ATen grid_sampler_2d_backward).
  * fmap [B][h][w][64]; xs [B][N][P] = priors_on_featmap (un-flipped); ys [P] = prior_feat_ys; out [B][N][P][64]. */

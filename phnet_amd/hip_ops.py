@@ -1061,6 +1061,49 @@ def lane_points(kept_rows, num, prior_ys, out=None):
     return out if batched else {k: v[0] for k, v in out.items()}
 
 
+LANE_TRACK_MAX_TRACKS, LANE_TRACK_MAX_OFFSETS = 64, 256       # limits of phnet_lane_track (csrc/lane_track.hip)
+LANE_TRACK_MAX_LDS_WORDS = 15360                              # (L + M) * S + 2 * L * M, the kernel's LDS staging
+
+
+def lane_track(kept_rows, num, state, thr: float, max_age: int, out=None):
+    """kept_rows [B,L,6+S] and num i64 [B] (one frame of B streams, T = 1) or [B,T,L,6+S] and [B,T] (T frames of each) as
+    lane_decode returns them; state: a phnet_amd.tracking.TrackState of those B streams (id, missed, hits i32 [B,M], ext i32
+    [B,M,2], x [B,M,S], next_id i32 [B]), advanced in place -> dict(track_id i32 [..,L], hits i32 [..,L]) shaped like num.
+    The rules are those of include/phnet_hip.h; thr is in the units of kept_rows.  One launch, everything stays on the device
+    (no sync).  out: such a dict to write into."""
+    _req(kept_rows, name="kept_rows"); _req(num, torch.int64, "num")
+    if kept_rows.dim() not in (3, 4):
+        raise ValueError("lane_track: kept_rows [B,L,6+S] or [B,T,L,6+S] expected")
+    b, t = kept_rows.shape[0], (kept_rows.shape[1] if kept_rows.dim() == 4 else 1)
+    l, s = kept_rows.shape[-2], kept_rows.shape[-1] - 6
+    lead = tuple(kept_rows.shape[:-2])
+    dev = kept_rows.device
+    if tuple(num.shape) != lead or num.device != dev:
+        raise ValueError(f"lane_track: kept_rows {tuple(kept_rows.shape)} vs num {tuple(num.shape)}")
+    m = state.id.shape[-1]
+    shapes = dict(id=((b, m), torch.int32), missed=((b, m), torch.int32), hits=((b, m), torch.int32), ext=((b, m, 2), torch.int32),
+                  x=((b, m, s), torch.float32), next_id=((b,), torch.int32))
+    for k, (shape, dt) in shapes.items():
+        v = _req(getattr(state, k), dt, "state." + k)
+        if tuple(v.shape) != shape or v.device != dev:
+            raise ValueError(f"lane_track: state.{k} must be {shape} on {dev}, got {tuple(v.shape)} on {v.device}")
+    if not (1 <= l <= m <= LANE_TRACK_MAX_TRACKS and 2 <= s <= LANE_TRACK_MAX_OFFSETS and (l + m) * s + 2 * l * m <= LANE_TRACK_MAX_LDS_WORDS):
+        raise ValueError(f"lane_track: L = {l}, M = {m}, S = {s} outside 1 <= L <= M <= 64, 2 <= S <= 256, (L + M) * S + 2 * L * M <= 15360")
+    outs = dict(track_id=(lead + (l,), torch.int32), hits=(lead + (l,), torch.int32))
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in outs.items()}
+    else:
+        for k, (shape, dt) in outs.items():
+            _req(out[k], dt, k + " out")
+            if tuple(out[k].shape) != shape or out[k].device != dev:
+                raise ValueError(f"lane_track: out[{k!r}] must be {shape}, got {tuple(out[k].shape)}")
+        out = {k: out[k] for k in outs}
+    check(lib().phnet_lane_track(_ptr(kept_rows), _ptr(num), b, t, l, s, m, float(thr), int(max_age), _ptr(state.id), _ptr(state.missed),
+                                 _ptr(state.hits), _ptr(state.ext), _ptr(state.x), _ptr(state.next_id), _ptr(out["track_id"]),
+                                 _ptr(out["hits"]), _stream()), "phnet_lane_track")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ Router4OLV2 family (inference)
 def gate_v2_fwd(x_cp, w1, s1, t1, w2, s2, t2, wl, bl, out: Optional[torch.Tensor] = None):
     """x_cp [M,C,P] -> sigmoid(mean(Linear(flatten(conv-bn-relu x2)))) [M]  (csrc/v2head.hip)."""

@@ -431,13 +431,29 @@ class DeviceResults:
         from phnet_amd import polylines as P
         return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
 
-    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False):
+    def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False,
+                    track: bool = False, max_tracks=None, max_age=None, match_thres=None):
         """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
         (phnet_amd.stream.LaneStream / LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.
-        polylines=True: the step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast())."""
+        polylines=True: the step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast()).
+        track=True: the step also gives every kept row a stable id (stream.tracks; defaults: tracking.track_defaults)."""
         from phnet_amd import stream
         return getattr(stream, self.stream_class)(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every,
-                                                  raw=raw, polylines=polylines)
+                                                  raw=raw, polylines=polylines, track=track, max_tracks=max_tracks, max_age=max_age,
+                                                  match_thres=match_thres)
+
+    def track_clips(self, kept_rows: torch.Tensor, nums: torch.Tensor, max_tracks=None, max_age=None, match_thres=None):
+        """Lane identities over the frames of a clip: kept_rows [T,max_lanes,6+S] / nums [T] of infer_device, or [B,T,..] / [B,T] of
+        infer_clips_device -> (track_id, hits), int32 shaped like nums + (max_lanes,).  One hip_ops.lane_track launch on a fresh
+        tracking.TrackState per clip (defaults: tracking.track_defaults); no host synchronisation."""
+        from phnet_amd import hip_ops as K
+        from phnet_amd.tracking import TrackState, track_defaults
+        M, age, thr = track_defaults(self, max_tracks, max_age, match_thres)
+        one = nums.dim() == 1
+        rows, n = (kept_rows[None], nums[None]) if one else (kept_rows, nums)
+        state = TrackState(rows.shape[0], M, rows.shape[-1] - 6, rows.device)
+        out = K.lane_track(rows.contiguous(), n.contiguous(), state, thr, age)
+        return (out["track_id"][0], out["hits"][0]) if one else (out["track_id"], out["hits"])
 
 
 BRANCH_B_SITES = 1 << 10     # dropout site numbering of branch B inside DropoutStream.items (functional.py)

@@ -9,7 +9,7 @@ they are; `Polyline.as_lane()` builds the reference-compatible `Lane` (with its 
     lines = to_host(pl["points"], pl["count"], pl["lanes_num"], pl["slot"], rows)
     lines[t][k].points                                                    # float64 [n,2], normalised (x, y)
 """
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -40,10 +40,13 @@ class Polyline:
         return f"[Polyline]\n{self.points}\n[/Polyline]"
 
 
-def to_host(points: torch.Tensor, count: torch.Tensor, lanes_num: torch.Tensor, slot: torch.Tensor, kept_rows: torch.Tensor) -> List:
+def to_host(points: torch.Tensor, count: torch.Tensor, lanes_num: torch.Tensor, slot: torch.Tensor, kept_rows: torch.Tensor,
+            track_id: Optional[torch.Tensor] = None) -> List:
     """points f32 [..,L,S,2], count i32 [..,L], lanes_num i32 [..], slot i32 [..,L] (hip_ops.lane_points) and the kept_rows
     [..,L,6+S] they were made from -> nested lists over the leading dimensions (streams; frames of a clip; clips x frames), the
-    innermost a list of Polyline per frame.  No leading dimension: the Polyline list of the one frame.
+    innermost a list of Polyline per frame.  No leading dimension: the Polyline list of the one frame.  track_id int32 [..,L]
+    (hip_ops.lane_track: the id of each kept_rows slot): each Polyline's metadata gains "track_id", a Python int, taken through
+    `slot` like the other keys; it travels in the same packed buffer.
 
     ONE device -> host transfer: the five tensors are PACKED on the device into one byte buffer (a single `torch.cat` launch of
     their byte views) and that buffer is copied once - five small copies would pay the copy latency five times, and a pinned
@@ -56,7 +59,9 @@ def to_host(points: torch.Tensor, count: torch.Tensor, lanes_num: torch.Tensor, 
                          f"slot {tuple(slot.shape)} / kept_rows {tuple(kept_rows.shape)} do not belong together")
     if (points.dtype, kept_rows.dtype) != (torch.float32, torch.float32) or any(t.dtype != torch.int32 for t in (count, lanes_num, slot)):
         raise ValueError("to_host: f32 points / kept_rows and int32 count / lanes_num / slot expected")
-    parts = (points, kept_rows, count, lanes_num, slot)                        # all 4-byte elements: one int32 buffer
+    if track_id is not None and (tuple(track_id.shape) != lead + (L,) or track_id.dtype != torch.int32):
+        raise ValueError(f"to_host: track_id must be int32 {lead + (L,)}, got {track_id.dtype} {tuple(track_id.shape)}")
+    parts = (points, kept_rows, count, lanes_num, slot) + (() if track_id is None else (track_id,))      # all 4-byte elements: one int32 buffer
     packed = torch.cat([t.detach().contiguous().view(torch.int32).reshape(-1) for t in parts]).cpu().numpy()
     views, at = [], 0
     for t in parts:
@@ -69,6 +74,11 @@ def to_host(points: torch.Tensor, count: torch.Tensor, lanes_num: torch.Tensor, 
     frames = [[Polyline(pts[f, k, :cnt[f, k]], {"start_x": meta[f, src[f, k], 2], "start_y": meta[f, src[f, k], 1],
                                                "conf": meta[f, src[f, k], 0]})
                for k in range(num[f])] for f in range(F)]
+    if track_id is not None:
+        ids = views[5].reshape(F, L)
+        for f in range(F):
+            for k, line in enumerate(frames[f]):
+                line.metadata["track_id"] = int(ids[f, src[f, k]])
     for n in reversed(lead[1:]):                                                # nest like the leading dimensions
         frames = [frames[i:i + n] for i in range(0, len(frames), n)]
     return frames if lead else frames[0]

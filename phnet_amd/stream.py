@@ -18,6 +18,10 @@ points on the device in `s.polylines` (points, count, lanes_num, slot); `s.lanes
 
     lines = s.lanes_fast()                                   # list over streams of phnet_amd.polylines.Polyline lists
 
+With `open_stream(..., track=True)` one launch after the decode (csrc/lane_track.hip, inside the captured graph, before the
+polylines) gives every kept row an id that stays with the lane from frame to frame; `s.tracks` holds `track_id` and `hits`
+(int32 [B,max_lanes], -1 / 0 where there is no lane) and `s.lanes_fast()` puts `track_id` into each polyline's metadata.
+
 `LaneStreamV2` is the same for the Router4OLV2 family (what `Router4OLV2.RouterOL.open_stream` returns): there the decoder runs
 for every stream and `stream_keys` (csrc/stream_v2.hip) picks each stream's key set - its memory window or its own tokens - from
 the device-side frame count.
@@ -93,10 +97,18 @@ class LaneStream:
     four device tensors for the last step (points [B,max_lanes,S,2], count, lanes_num, slot) and `lanes_fast()` reads them.  What
     `step` returns does not change.
 
-    With graph=True the returned tensors (and `polylines`) are the graph's static outputs: the next `step` overwrites them."""
+    track=True: the launch after the decode (inside the captured graph, before the polylines) is `hip_ops.lane_track` on a
+    `tracking.TrackState` of max_tracks slots per stream (`track_state`); `tracks` = dict(track_id, hits), int32 [B,max_lanes],
+    is written by every step.  max_tracks / max_age / match_thres (pixels of the network input): tracking.track_defaults.
+    `reset(mask)` also frees the tracks of those streams (their next ids are new ones); `reset_every` resets the memory only -
+    it is an evaluation protocol within one video, so ids carry across the chunk boundary.  Without track=True nothing is
+    allocated, launched or returned differently.
+
+    With graph=True the returned tensors (and `polylines`, `tracks`) are the graph's static outputs: the next `step` overwrites them."""
 
     def __init__(self, model, streams: int = 1, frame_hw: Tuple[int, int] = None, graph: bool = True, reset_every: Optional[int] = None,
-                 raw=None, warmup: int = 2, polylines: bool = False):
+                 raw=None, warmup: int = 2, polylines: bool = False, track: bool = False, max_tracks: Optional[int] = None,
+                 max_age: Optional[int] = None, match_thres: Optional[float] = None):
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
         det = model.head
@@ -108,6 +120,12 @@ class LaneStream:
         self.model, self.streams, self.reset_every, self.raw = model.eval(), int(streams), reset_every, raw
         self.want_polylines, self.polylines = bool(polylines), None
         self.state = self._new_state(det, dev)
+        self.track_state, self.tracks = None, None
+        if track:
+            from .tracking import TrackState, track_defaults
+            M, self.max_age, self.match_thr = track_defaults(model, max_tracks, max_age, match_thres)
+            self.track_state = TrackState(self.streams, M, det.n_offsets, dev)
+            self.tracks = {k: torch.zeros((self.streams, det.cfg.max_lanes), dtype=torch.int32, device=dev) for k in ("track_id", "hits")}
         if raw is not None:
             if (raw.out_h, raw.out_w) != tuple(frame_hw):
                 raise ValueError(f"raw= resizes to {raw.out_h}x{raw.out_w}, frame_hw is {tuple(frame_hw)}")
@@ -123,6 +141,8 @@ class LaneStream:
                 self.out = self._body(self.frames)
             torch.cuda.synchronize()
         self.reset()                                              # the warm-up frames are forgotten
+        if self.track_state is not None:
+            self.track_state.next_id.fill_(1)                     # and so are the ids they used
 
     def _new_state(self, det, dev) -> StreamState:
         return StreamState(det.refine_layers, self.streams, self.model.save_freq_max, det.cfg.max_lanes, det.num_priors,
@@ -144,7 +164,11 @@ class LaneStream:
         return self._result(det, dec)
 
     def _result(self, det, dec):
-        """What `step` returns; with polylines=True the lane points of this frame first, as the last launch of the step."""
+        """What `step` returns; first, with track=True, the ids of this frame's lanes and, with polylines=True, their points as
+        the last launch of the step."""
+        if self.track_state is not None:
+            K.lane_track(dec["kept_rows"].contiguous(), dec["num"].contiguous(), self.track_state, self.match_thr, self.max_age,
+                         out=self.tracks)
         if self.want_polylines:
             self.polylines, self._rows = det.points_device(dec), dec["kept_rows"]      # the rows `slot` points into
         return dec["kept_rows"], dec["num"], dec["anchors"]
@@ -159,6 +183,8 @@ class LaneStream:
                 raise ValueError(f"reset: bool mask of {self.streams} streams expected")
             mask = mask.reshape(-1).to(self.state.n.device, non_blocking=True)
         self.state.reset(mask)
+        if self.track_state is not None:
+            self.track_state.reset(mask)
 
     def step(self, frames: torch.Tensor):
         """One frame of every stream: frames f32 [B,3,H,W] (u8 [B,src_h,src_w,3] with raw=) on the device ->
@@ -181,11 +207,13 @@ class LaneStream:
 
     def lanes_fast(self) -> Sequence[list]:
         """The lanes of the last step from the device-side polylines: one device -> host copy, numpy slicing, no splines
-        (phnet_amd.polylines.to_host).  A list over streams of Polyline lists, lane for lane the points of `lanes`."""
+        (phnet_amd.polylines.to_host).  A list over streams of Polyline lists, lane for lane the points of `lanes`; with
+        track=True each Polyline's metadata carries its lane's "track_id"."""
         if self.polylines is None:
             raise RuntimeError("lanes_fast: open the stream with polylines=True and run a step first")
         from . import polylines as P
-        return P.to_host(self.polylines["points"], self.polylines["count"], self.polylines["lanes_num"], self.polylines["slot"], self._rows)
+        return P.to_host(self.polylines["points"], self.polylines["count"], self.polylines["lanes_num"], self.polylines["slot"], self._rows,
+                         track_id=None if self.tracks is None else self.tracks["track_id"])
 
 
 class LaneStreamV2(LaneStream):
