@@ -248,6 +248,22 @@ int phnet_lane_raster(const int32_t* segs, int64_t n_segs, uint32_t* masks, int3
                       int32_t lane_width, void* stream);
 int phnet_lane_mask_stats(const uint32_t* masks, int32_t n_lanes, int32_t height, int32_t width, const int32_t* pairs,
                           int32_t n_pairs, int64_t* area, int64_t* inter, void* stream);
+/* IoU MATRICES straight from the masks of phnet_lane_raster (the temporal evaluator, evaluation/evalTemporalOLV2.py:26-35,
+ * and any caller that wants matrices instead of counts).  groups [n_groups][5] int32 in device memory = (row_first, n_rows,
+ * col_first, n_cols, out_first): group g is the matrix of lanes row_first.. against lanes col_first.., its entry (r, c) is
+ * iou[out_first + r * n_cols + c]; out_first[0] = 0 and out_first[g + 1] = out_first[g] + n_rows * n_cols (n_rows or n_cols
+ * may be 0); n_entries = their total, passed by the caller because the host never reads `groups`.  With I, A, B the set bits
+ * of a & b, a, b (int64) and U = A + B - I:  iou = (double)(scale * I) / ((double)(scale * U) + eps) - integer products,
+ * one conversion each, one double add, one IEEE divide (no floating multiply, so nothing to fuse).  scale = 1, eps = 0 is
+ * I / (A + B - I) with 0 / 0 = NaN; scale = 3, eps = 1e-10 the reference's three-channel canvases.  area (may be NULL) [n_lanes]
+ * int64 receives every lane's set bits.  One workgroup per entry (and per lane for `area`) reads both masks once; no atomics:
+ * every iou[0 .. n_entries) and every area[lane] is written on every call, nothing has to be zeroed, the result does not
+ * depend on scheduling.  An entry whose lane index is outside [0, n_lanes), or that the table does not cover, is skipped.
+ * height, width 1..4096; scale >= 1; eps finite and >= 0; n_entries + n_lanes < 2^31; n_groups == 0 or n_entries == 0
+ * without `area` is a no-op. */
+int phnet_lane_iou_groups(const uint32_t* masks, int32_t n_lanes, int32_t height, int32_t width, const int32_t* groups,
+                          int32_t n_groups, int64_t n_entries, int32_t scale, double eps, double* iou, int64_t* area,
+                          void* stream);
 
 /* ---- MaxPool2d(3,2,1): libs/models/resnet.py:217,297 ---- */
 int phnet_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* argmax, int32_t N, int32_t Hi, int32_t Wi, int32_t C, void* stream);

@@ -12,7 +12,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "phnet_hip.h")
 TUNING_HEADER = os.path.join(os.path.dirname(_HERE), "include", "phnet_hip_tuning.h")    # benchmark / A-B switches, not the boundary
 
 _CTYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
-           "float": ctypes.c_float, "int": ctypes.c_int, "void": None}
+           "float": ctypes.c_float, "double": ctypes.c_double, "int": ctypes.c_int, "void": None}
 
 ERRORS = {-1: "PHNET_ERR_ARG (bad shape / null pointer / unsupported size)",
           -2: "PHNET_ERR_WORKSPACE (workspace too small)",

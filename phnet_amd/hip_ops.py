@@ -1249,6 +1249,49 @@ def lane_mask_iou(segs, n_lanes: int, pairs, height: int, width: int, lane_width
     return lane_mask_stats(lane_raster(segs, n_lanes, height, width, lane_width), pairs, width)
 
 
+def check_iou_groups(groups, n_lanes: int):
+    """Host check of a `phnet_lane_iou_groups` table -> (int32 [G, 5] array, n_entries).  Rows are (row_first, n_rows, col_first,
+    n_cols, out_first): counts >= 0, lane ranges inside [0, n_lanes), out_first = 0 and then ascending without gaps."""
+    import numpy as np
+    g = np.asarray(groups)
+    if g.size == 0:
+        g = np.zeros((0, 5), np.int32)
+    if g.ndim != 2 or g.shape[1] != 5 or g.dtype.kind not in "iu":
+        raise ValueError("lane_iou_groups: groups must be an integer table [n_groups, 5]")
+    g = g.astype(np.int64)
+    total = 0
+    for k, (r0, nr, c0, nc, out) in enumerate(g.tolist()):
+        if nr < 0 or nc < 0:
+            raise ValueError(f"lane_iou_groups: group {k} has a negative count")
+        if (nr and (r0 < 0 or r0 + nr > n_lanes)) or (nc and (c0 < 0 or c0 + nc > n_lanes)):
+            raise ValueError(f"lane_iou_groups: group {k} addresses a lane outside [0, {n_lanes})")
+        if out != total:
+            raise ValueError(f"lane_iou_groups: group {k} has out_first {out}, contiguous output wants {total}")
+        total += nr * nc
+    if total + n_lanes >= 1 << 31:
+        raise ValueError("lane_iou_groups: too many entries for one launch")
+    return np.ascontiguousarray(g.astype(np.int32)), total
+
+
+def lane_iou_groups(masks, groups, width: int, scale: int = 1, eps: float = 0.0, want_area: bool = False):
+    """IoU matrices of the masks of `lane_raster`, one launch (csrc/lane_iou.hip): `groups` is a HOST integer table [G][5] =
+    (row_first, n_rows, col_first, n_cols, out_first), checked here before it is uploaded; -> iou float64 [n_entries], entry
+    (r, c) of group g at out_first + r * n_cols + c = scale * I / (scale * (A + B - I) + eps) (and area int64 [n_lanes])."""
+    n_lanes = int(masks.shape[0])
+    table, n_entries = check_iou_groups(groups, n_lanes)
+    if int(scale) < 1 or not (0.0 <= float(eps) < float("inf")):
+        raise ValueError("lane_iou_groups: scale must be >= 1 and eps finite and >= 0")
+    _req(masks, torch.int32, "masks")
+    height = masks.shape[1]
+    assert masks.dim() == 3 and masks.shape[2] == (width + 31) // 32
+    dev_groups = torch.from_numpy(table).to(masks.device)
+    iou = torch.empty(n_entries, dtype=torch.float64, device=masks.device)
+    area = torch.empty(n_lanes, dtype=torch.int64, device=masks.device) if want_area else None
+    check(lib().phnet_lane_iou_groups(_ptr(masks), n_lanes, height, width, _ptr(dev_groups), table.shape[0], n_entries, int(scale),
+                                      float(eps), _ptr(iou), _ptr(area), _stream()), "phnet_lane_iou_groups")
+    return (iou, area) if want_area else iou
+
+
 def tune_k_tile(code: int) -> None:
     """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on."""
     check(lib().phnet_tune_force_k_tile(code), "phnet_tune_force_k_tile")
