@@ -235,6 +235,24 @@ int phnet_preprocess_u8(const uint8_t* frames, float* out, uint8_t* out_u8,
                         const int32_t* xi, const int16_t* xc, const int32_t* yi, const int16_t* yc,
                         int32_t T, int32_t H0, int32_t W0, int32_t crop_top, int32_t out_h, int32_t out_w, int32_t flip,
                         int32_t layout, const float* mean3_host, const float* std3_host, void* stream);
+/* The same launch on camera surfaces (no RGB image in memory).  frames: T surfaces frame_stride bytes apart.  format 0 = NV12:
+ * H0 luma rows of `pitch` bytes, then from byte chroma_offset (>= pitch * H0) on H0/2 rows of interleaved U,V, `pitch` bytes
+ * each; format 1 = YUYV: H0 rows of `pitch` bytes Y0 U Y1 V (chroma_offset ignored).  pitch >= W0 (NV12) / 2 W0 (YUYV).
+ * Colour of source pixel (r, x), r counted in the UNCROPPED frame, in int32:
+ *   c = clamp((m[c][0] (Y - y0) + m[c][1] (U - 128) + m[c][2] (V - 128) + 2^19) >> 20, 0, 255)   (arithmetic shift)
+ * csc_host [10] (HOST pointer) = y0, then m row-major (rows R, G, B; columns Y, U, V), 20-bit fixed point; 0 <= y0 <= 255 and
+ * 255 * (|m[c][0]| + |m[c][1]| + |m[c][2]|) + 2^19 < 2^31.  Chroma is replicated, never interpolated: NV12 reads
+ * uv[(r >> 1) * pitch + 2 (x >> 1) + {0, 1}] (an odd crop_top therefore changes the chroma parity of the cropped rows), YUYV
+ * Y = row[2 x], U, V = row[4 (x >> 1) + {1, 3}].  Flip mirrors x before the colour lookup.  From the 8-bit colours on everything
+ * is phnet_preprocess_u8 bit for bit (same tables, taps, rounding, normalisation, layouts, out_u8).  Bytes of a row beyond W0
+ * (2 W0) and rows beyond H0 are never read.  PHNET_ERR_ARG before any launch: odd W0, odd H0 with NV12, pitch or chroma_offset
+ * too small, frame_stride smaller than the bytes a frame spans, unknown format / layout, crop_top outside [0, H0), a null
+ * pointer, a zero std, a matrix outside the bound above.  T == 0 is a no-op. */
+int phnet_preprocess_yuv(const uint8_t* frames, float* out, uint8_t* out_u8,
+                         const int32_t* xi, const int16_t* xc, const int32_t* yi, const int16_t* yc,
+                         int32_t T, int32_t H0, int32_t W0, int32_t crop_top, int32_t out_h, int32_t out_w, int32_t flip, int32_t layout,
+                         int32_t format, int64_t frame_stride, int32_t pitch, int64_t chroma_offset,
+                         const int32_t* csc_host, const float* mean3_host, const float* std3_host, void* stream);
 
 /* ---- lane IoU of the CULane-style evaluator: replaces LaneCompare::get_lane_similarity's two
  * cv::Mat canvases + cv::line + cv::sum (evaluation/culane/src/lane_compare.cpp:11-57).  A lane is a bit mask

@@ -91,7 +91,8 @@ class LaneStream:
     (warmed up and captured the way GraphedInference does it) and replayed for every frame - a reset never recaptures;
     graph=False runs the same launches eagerly.  reset_every=k resets all streams before frames 0, k, 2k, ... (k = 16 is the
     chunking of the reference's testOL.py:104-117).  raw: a ClipPreprocessor - `step` then takes camera-format uint8 frames
-    [B,src_h,src_w,3] and the crop / resize / normalise launch is part of the step (and of the captured graph).
+    [B, *raw.frame_shape] (packed RGB [B,src_h,src_w,3], or the NV12 / YUYV surfaces of a ClipPreprocessor built with pixel_format=)
+    and the colour conversion / crop / resize / normalise launch is part of the step (and of the captured graph).
 
     polylines=True: the last launch of the step (inside the captured graph) is `hip_ops.lane_points`; `polylines` then holds its
     four device tensors for the last step (points [B,max_lanes,S,2], count, lanes_num, slot) and `lanes_fast()` reads them.  What
@@ -129,7 +130,7 @@ class LaneStream:
         if raw is not None:
             if (raw.out_h, raw.out_w) != tuple(frame_hw):
                 raise ValueError(f"raw= resizes to {raw.out_h}x{raw.out_w}, frame_hw is {tuple(frame_hw)}")
-            self.frames = torch.zeros((self.streams, raw.src_h, raw.src_w, 3), dtype=torch.uint8, device=dev)
+            self.frames = torch.zeros((self.streams, *raw.frame_shape), dtype=torch.uint8, device=dev)
         else:
             self.frames = torch.zeros((self.streams, 3, *frame_hw), dtype=torch.float32, device=dev)
         self.frame_index = 0                                      # host-side count of steps, for reset_every only
@@ -187,7 +188,7 @@ class LaneStream:
             self.track_state.reset(mask)
 
     def step(self, frames: torch.Tensor):
-        """One frame of every stream: frames f32 [B,3,H,W] (u8 [B,src_h,src_w,3] with raw=) on the device ->
+        """One frame of every stream: frames f32 [B,3,H,W] (u8 [B, *raw.frame_shape] with raw=) on the device ->
         (kept_rows [B,max_lanes,6+S], num [B], anchors [B,max_lanes]) on the device.  No host synchronisation."""
         if frames.shape != self.frames.shape or frames.dtype != self.frames.dtype or not frames.is_cuda:
             raise ValueError(f"step: {self.frames.dtype} device frames {tuple(self.frames.shape)} expected, "
