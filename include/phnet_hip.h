@@ -94,6 +94,33 @@ int phnet_lane_track(const float* kept_rows, const int64_t* num, int64_t B, int3
                      int32_t max_age, int32_t* trk_id, int32_t* trk_missed, int32_t* trk_hits, int32_t* trk_ext, float* trk_x,
                      int32_t* next_id, int32_t* track_id, int32_t* track_hits, void* stream);
 
+/* ---- training targets: annotated lane points -> the label rows the criterion consumes (csrc/lane_targets.hip; replaces the label
+ * half of the reference's per-frame pipeline: datasetOL.py:47-59 crop / flip, transforms.py:251-347 transform_annotation,
+ * filter_lane, sample_lane).  One launch for F frames, one wavefront per (frame, output row), no host synchronisation.
+ * points f32 [F][Lin][P][2] (x, y), counts i32 [F][Lin] (clamped to [0, P]), lanes_num i32 [F] (clamped to [0, Lin]); entries
+ * beyond a count are never read.  offsets_ys f64 [S] on the device: the reference's np.arange(img_h, -1, -strip_size), strictly
+ * descending, taken as numpy builds it (its last entry is not exactly 0).  out f32 [F][R][6+S], every element written on every
+ * call.  Float64 throughout (input points widened exactly), nothing contracted, one cast to float32 at the end.
+ * Per frame:
+ *   0. map, per point: y = y - crop; flip: x = (src_w - 1) - x; x = x * scale_x; y = y * scale_y.
+ *   1. lanes with more than 2 points survive and are numbered in order; number r owns row r; numbers >= R are ignored.
+ *   2. default row: [0] = 1, [1] = 0, the rest -1e5.  Rows without a lane, and lanes with a non-finite mapped coordinate, keep it.
+ *   3. stable sort by descending y; of equal y the first in input order stays; x = (x * img_w) / img_w, y = (y * img_h) / img_h.
+ *      n points remain; n < 2 keeps the default row.
+ *   4. interpolant over ascending y: n = 2 the line, n = 3 the parabola (Newton form), n >= 4 the not-a-knot cubic spline (knot
+ *      derivatives by a tridiagonal solve without pivoting; Horner evaluation in the interval found by binary search).
+ *   5. table order: ys > y_max: the line through the two bottom-most points; y_min <= ys <= y_max: the interpolant; ys < y_min:
+ *      dropped.  No row of the second kind keeps the default row.
+ *   6. inside iff 0 <= x < img_w.  All outside values come first, then the inside ones, each in table order.
+ *   7. n_in <= 1 keeps the default row.  Else [0] = 0, [1] = 1, [2] = n_out / (S-1), [3] = inside[0] / (img_w - 1), [4] = mean over
+ *      i = 1..n_in-1 of t_i = atan(i * strip_size / (inside[i] - inside[0] + 1e-5)) / pi (1 - |t_i| where not t_i > 0), summed in
+ *      ascending i, [5] = n_in / (S-1), [6..] = the values of rule 6, then -1e5.
+ * Limits (PHNET_ERR_ARG before any launch): 1 <= F < 2^31, 1 <= Lin <= 64, 2 <= P <= 256, 1 <= R <= 64, 2 <= S <= 256; img_h,
+ * img_w, strip_size, scale_x, scale_y finite and > 0; crop and src_w finite; flip 0 or 1; all pointers non-null. */
+int phnet_lane_targets(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys, float* out,
+                       int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
+                       double crop, double src_w, double scale_x, double scale_y, int32_t flip, void* stream);
+
 /* ---- lane-anchor ROI pooling: replaces F.grid_sample(..., align_corners=True) + permutes
  * (libs/models/Router4OL.py:132-150, 269-272) and its backward (ATen grid_sampler_2d_backward).
  * fmap [B][h][w][64]; xs [B][N][P] = priors_on_featmap (un-flipped); ys [P] = prior_feat_ys; out [B][N][P][64]. */

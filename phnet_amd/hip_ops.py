@@ -1104,6 +1104,38 @@ def lane_track(kept_rows, num, state, thr: float, max_age: int, out=None):
     return out
 
 
+LANE_TARGETS_MAX_IN_LANES, LANE_TARGETS_MAX_POINTS = 64, 256       # limits of phnet_lane_targets (csrc/lane_targets.hip)
+LANE_TARGETS_MAX_ROWS, LANE_TARGETS_MAX_OFFSETS = 64, 256
+
+
+def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: float, img_w: float, strip_size: float,
+                 crop: float = 0.0, src_w: float = 0.0, scale_x: float = 1.0, scale_y: float = 1.0, flip: bool = False, out=None):
+    """points [F,Lin,P,2], counts i32 [F,Lin], lanes_num i32 [F], offsets_ys f64 [S] (the reference's np.arange table, on the
+    device) -> label rows [F,max_lanes,6+S] by the rules of include/phnet_hip.h.  One launch, no allocation with out=, no sync."""
+    _req(points, name="points"); _req(counts, torch.int32, "counts"); _req(lanes_num, torch.int32, "lanes_num")
+    _req(offsets_ys, torch.float64, "offsets_ys")
+    if points.dim() != 4 or points.shape[-1] != 2 or offsets_ys.dim() != 1:
+        raise ValueError("lane_targets: points [F,Lin,P,2] and offsets_ys [S] expected")
+    f, lin, p, _ = points.shape
+    s, r, dev = offsets_ys.shape[0], int(max_lanes), points.device
+    if tuple(counts.shape) != (f, lin) or tuple(lanes_num.shape) != (f,) or any(t.device != dev for t in (counts, lanes_num, offsets_ys)):
+        raise ValueError(f"lane_targets: points {tuple(points.shape)} vs counts {tuple(counts.shape)}, lanes_num {tuple(lanes_num.shape)}")
+    if not (1 <= f < 2 ** 31 and 1 <= lin <= LANE_TARGETS_MAX_IN_LANES and 2 <= p <= LANE_TARGETS_MAX_POINTS
+            and 1 <= r <= LANE_TARGETS_MAX_ROWS and 2 <= s <= LANE_TARGETS_MAX_OFFSETS):
+        raise ValueError(f"lane_targets: F = {f}, Lin = {lin}, P = {p}, R = {r}, S = {s} outside 1 <= F < 2^31, 1 <= Lin <= 64, "
+                         "2 <= P <= 256, 1 <= R <= 64, 2 <= S <= 256")
+    if out is None:
+        out = torch.empty((f, r, 6 + s), dtype=torch.float32, device=dev)
+    else:
+        _req(out, name="out")
+        if tuple(out.shape) != (f, r, 6 + s) or out.device != dev:
+            raise ValueError(f"lane_targets: out must be {(f, r, 6 + s)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    check(lib().phnet_lane_targets(_ptr(points), _ptr(counts), _ptr(lanes_num), _ptr(offsets_ys), _ptr(out), f, lin, p, r, s, float(img_h),
+                                   float(img_w), float(strip_size), float(crop), float(src_w), float(scale_x), float(scale_y), int(bool(flip)),
+                                   _stream()), "phnet_lane_targets")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ Router4OLV2 family (inference)
 def gate_v2_fwd(x_cp, w1, s1, t1, w2, s2, t2, wl, bl, out: Optional[torch.Tensor] = None):
     """x_cp [M,C,P] -> sigmoid(mean(Linear(flatten(conv-bn-relu x2)))) [M]  (csrc/v2head.hip)."""

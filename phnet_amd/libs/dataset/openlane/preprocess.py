@@ -3,8 +3,9 @@ normalised float clip the model consumes.
 
 Replaces the image half of the reference's per-frame CPU pipeline (libs/dataset/openlane/datasetOL.py:40-52 crop / flip,
 transforms.py:150-156 iaa.Resize = cv2 INTER_CUBIC on uint8, datasetOL.py:63-75 ToTensor + Normalize, :11-17 stacking) with ONE
-launch per clip (csrc/preprocess.hip).  The label half (lane resampling, transforms.py:100-147 / 264-297) is host-side
-geometry on a handful of points and stays where it is.  No CPU path: the frames must already be on the device.
+launch per clip (csrc/preprocess.hip).  The label half (annotated points -> the [max_lanes, 6+S] target rows,
+transforms.py:251-347) is `TargetEncoder` in targets.py beside this file; `TargetEncoder.for_preprocessor(pre, ...)` takes its
+geometry from a ClipPreprocessor.  No CPU path: the frames must already be on the device.
 
 Arithmetic: OpenCV's 8-bit bicubic resize as published (half-pixel centres, a = -0.75 kernel, 11-bit fixed-point taps that
 sum to 2048, replicated borders, rounding 22-bit shift, saturation).  PARITY UNPINNED: cv2 / imgaug are not installed here

@@ -1,0 +1,100 @@
+"""Training targets on the GPU: annotated lane points -> the [max_lanes, 6+S] label rows that Criterion4OL and
+GraphedTrainStep(frames, lanes) consume.
+
+Replaces the label half of the reference's per-frame CPU pipeline (libs/dataset/openlane/datasetOL.py:47-59 crop / flip,
+transforms.py:251-347 transform_annotation / filter_lane / sample_lane, which runs behind imgaug and scipy) with ONE launch for all
+frames (csrc/lane_targets.hip); `ClipPreprocessor` is the image half.  No CPU path: the points must already be on the device
+(`pack_annotations` pads Python / numpy annotation lists into pinned host tensors to copy from).
+
+Arithmetic: the reference's float64 path, rule by rule (include/phnet_hip.h), with scipy's InterpolatedUnivariateSpline solved
+explicitly (line, parabola, not-a-knot cubic spline).  Pinned to the reference's own executed code on tests/golden/targets_tiny.json.
+PARITY UNPINNED (imgaug is not installed here): the arithmetic of its Resize on line strings - this module uses x * (out_w / src_w)
+and y * (out_h / (src_h - crop)), each ratio formed once in double - and clip_out_of_image_(), which is not built: points outside
+the image are kept (DESIGN.md "Training targets")."""
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from phnet_amd import hip_ops as K
+
+
+def sample_rows(img_h: int, num_points: int) -> np.ndarray:
+    """cfg.offsets_ys of options4OL.py:146-148, exactly as numpy builds it: float64, bottom to top; its last entry is not exactly
+    0 (-8.5e-13 for 320 / 35), so a lane whose top point has y == 0.0 does not get that row."""
+    strip_size = img_h / (num_points - 1)
+    ys = np.arange(img_h, -1, -strip_size)
+    if len(ys) != num_points:
+        raise ValueError(f"np.arange({img_h}, -1, -{img_h}/{num_points - 1}) has {len(ys)} entries, not num_points = {num_points}")
+    return ys
+
+
+class TargetEncoder:
+    """cfg-like arguments as in options/options4OL.py (height, width, num_points, max_lanes; org 1280x1920, crop_size 480)."""
+
+    def __init__(self, out_h: int, out_w: int, num_points: int, max_lanes: int, src_h: int = 1280, src_w: int = 1920,
+                 crop_size: int = 480, device="cuda"):
+        self.out_h, self.out_w, self.src_h, self.src_w, self.crop = int(out_h), int(out_w), int(src_h), int(src_w), int(crop_size)
+        self.num_points, self.max_lanes = int(num_points), int(max_lanes)
+        if not 0 <= self.crop < self.src_h:
+            raise ValueError("crop_size must leave at least one row")
+        if not (2 <= self.num_points <= K.LANE_TARGETS_MAX_OFFSETS and 1 <= self.max_lanes <= K.LANE_TARGETS_MAX_ROWS):
+            raise ValueError(f"num_points = {num_points}, max_lanes = {max_lanes} outside 2 <= S <= 256, 1 <= R <= 64")
+        self.strip_size = self.out_h / (self.num_points - 1)
+        self.scale_x = float(self.out_w) / float(self.src_w)
+        self.scale_y = float(self.out_h) / float(self.src_h - self.crop)
+        self.offsets_ys = torch.from_numpy(sample_rows(self.out_h, self.num_points)).to(torch.device(device))
+
+    @classmethod
+    def for_preprocessor(cls, pre, num_points: int, max_lanes: int) -> "TargetEncoder":
+        """The label half of a ClipPreprocessor: same output size, source size, crop and device."""
+        return cls(pre.out_h, pre.out_w, num_points, max_lanes, src_h=pre.src_h, src_w=pre.src_w, crop_size=pre.crop, device=pre.xi.device)
+
+    def __call__(self, points: torch.Tensor, counts: torch.Tensor, lanes_num: torch.Tensor, flip: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """points f32 [T,Lin,P,2] in source (camera) pixels, counts i32 [T,Lin], lanes_num i32 [T], all on the device (leading
+        dimensions [B,T] are accepted) -> float32 [T,max_lanes,6+S].  flip: the clip was mirrored (datasetOL.py:54-55).
+        out: a buffer of that shape to write into, e.g. the `lanes` of a GraphedTrainStep - then nothing is allocated and nothing
+        waits for the device, so the call can be captured in a graph."""
+        if not (points.is_cuda and counts.is_cuda and lanes_num.is_cuda):
+            raise RuntimeError("TargetEncoder: CUDA(HIP) tensors expected; phnet_amd has no CPU path")
+        if points.dim() < 4 or points.shape[-1] != 2:
+            raise ValueError("TargetEncoder: points [..,Lin,P,2] expected")
+        lead, (lin, p) = tuple(points.shape[:-3]), points.shape[-3:-1]
+        if tuple(counts.shape) != lead + (lin,) or tuple(lanes_num.shape) != lead:
+            raise ValueError(f"TargetEncoder: points {tuple(points.shape)} vs counts {tuple(counts.shape)}, lanes_num {tuple(lanes_num.shape)}")
+        shape = lead + (self.max_lanes, 6 + self.num_points)
+        if out is not None and tuple(out.shape) != shape:
+            raise ValueError(f"TargetEncoder: out must be {shape}, got {tuple(out.shape)}")
+        for t, name in ((points, "points"), (counts, "counts"), (lanes_num, "lanes_num"), (out, "out")):
+            if t is not None and not t.is_contiguous():
+                raise RuntimeError(f"TargetEncoder: {name} must be contiguous")
+        flat = K.lane_targets(points.view(-1, lin, p, 2), counts.view(-1, lin), lanes_num.view(-1), self.offsets_ys, self.max_lanes,
+                              self.out_h, self.out_w, self.strip_size, crop=self.crop, src_w=self.src_w, scale_x=self.scale_x,
+                              scale_y=self.scale_y, flip=flip, out=None if out is None else out.view(-1, self.max_lanes, 6 + self.num_points))
+        return flat.view(shape) if out is None else out
+
+
+def pack_annotations(frames_of_lanes: Sequence, max_in_lanes: int, max_points: int):
+    """Host helper: [frame][lane] -> array-like [n, 2] of (x, y) -> (points f32 [T,max_in_lanes,max_points,2], counts i32
+    [T,max_in_lanes], lanes_num i32 [T]), zero padded, in pinned memory where a device is present (copy with non_blocking=True).
+    A frame with more than max_in_lanes lanes or a lane with more than max_points points raises: nothing is truncated."""
+    if not (1 <= max_in_lanes <= K.LANE_TARGETS_MAX_IN_LANES and 2 <= max_points <= K.LANE_TARGETS_MAX_POINTS):
+        raise ValueError(f"max_in_lanes = {max_in_lanes}, max_points = {max_points} outside 1 <= Lin <= 64, 2 <= P <= 256")
+    t = len(frames_of_lanes)
+    points = np.zeros((t, max_in_lanes, max_points, 2), np.float32)
+    counts = np.zeros((t, max_in_lanes), np.int32)
+    lanes_num = np.zeros((t,), np.int32)
+    for f, lanes in enumerate(frames_of_lanes):
+        if len(lanes) > max_in_lanes:
+            raise ValueError(f"frame {f} has {len(lanes)} lanes, max_in_lanes = {max_in_lanes}")
+        lanes_num[f] = len(lanes)
+        for l, lane in enumerate(lanes):
+            pts = np.asarray(lane, dtype=np.float32).reshape(-1, 2) if len(lane) else np.zeros((0, 2), np.float32)
+            if len(pts) > max_points:
+                raise ValueError(f"lane {l} of frame {f} has {len(pts)} points, max_points = {max_points}")
+            counts[f, l] = len(pts)
+            points[f, l, :len(pts)] = pts
+    pin = torch.cuda.is_available()
+    tensors = tuple(torch.from_numpy(a) for a in (points, counts, lanes_num))
+    return tuple(x.pin_memory() for x in tensors) if pin else tensors
