@@ -120,6 +120,16 @@ int phnet_lane_track(const float* kept_rows, const int64_t* num, int64_t B, int3
 int phnet_lane_targets(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys, float* out,
                        int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
                        double crop, double src_w, double scale_x, double scale_y, int32_t flip, void* stream);
+/* The same launch behind an augmented image (phnet_augment_u8 below): one rule more, after rule 0, in output pixels:
+ *   0b. flip2[f] != 0: x = (img_w - 1) - x; then (x, y) = ((f00 x + f01 y) + f02, (f10 x + f11 y) + f12), f = fwd[f] - float64, not
+ *       contracted.  Everything from rule 1 on is unchanged: a lane that the rotation makes non-monotonic in y goes through the sort
+ *       and the de-duplication of rule 3, a non-finite product keeps the default row (rule 2).
+ * flip2 i32 [F], fwd f64 [F][6] (the source -> output matrix, row-major 2 x 3: the inverse of the image's matrix), on the device;
+ * either may be null and its step is skipped: with both null this is phnet_lane_targets, bit for bit.  Limits as above. */
+int phnet_lane_targets_aug(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys, float* out,
+                           int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
+                           double crop, double src_w, double scale_x, double scale_y, int32_t flip, const int32_t* flip2,
+                           const double* fwd, void* stream);
 
 /* ---- lane-anchor ROI pooling: replaces F.grid_sample(..., align_corners=True) + permutes
  * (libs/models/Router4OL.py:132-150, 269-272) and its backward (ATen grid_sampler_2d_backward).
@@ -280,6 +290,49 @@ int phnet_preprocess_yuv(const uint8_t* frames, float* out, uint8_t* out_u8,
                          int32_t T, int32_t H0, int32_t W0, int32_t crop_top, int32_t out_h, int32_t out_w, int32_t flip, int32_t layout,
                          int32_t format, int64_t frame_stride, int32_t pitch, int64_t chroma_offset,
                          const int32_t* csc_host, const float* mean3_host, const float* std3_host, void* stream);
+
+/* ---- training augmentation of a clip (csrc/augment.hip): the point-wise ops and the affine of the reference's imgaug pipeline
+ * (transforms.py:190-249: HorizontalFlip, ChannelShuffle, MultiplyAndAddToBrightness, AddToHueAndSaturation, Dropout / CoarseDropout,
+ * Affine with mode = 'constant', cval = 0) on the RESIZED 8-bit image, in the reference's order with the affine last, in one launch and
+ * without an intermediate image; its blurs and edge filters are not built.  PARITY UNPINNED against imgaug / cv2 (DESIGN.md "Training
+ * augmentation"): the rules below are the definition.
+ * frames u8 [T][H][W][3] on the device (the out_u8 of phnet_preprocess_u8 / _yuv); out f32 NCHW [T][3][H][W] (layout 0) or NHWC4
+ * [T][H][W][4] (layout 1); out_u8 optional [T][H][W][3], the augmented 8-bit image; mean3 / std3 HOST pointers.  Per-frame parameters,
+ * all on the device and read by the kernel (a replayed graph sees what they hold then): flip2 i32 [T]; inv f64 [T][6], the
+ * output -> source matrix a, row-major 2 x 3; table i32 [T][16] with columns 0-2 perm, 3 mq, 4 add, 5 value, 6 dropout mode, 7
+ * per_channel, 8 threshold (the uint32 bits), 9 gh, 10 gw, 11 / 12 the low / high 32 bits of the frame's seed, 13-15 unused.
+ * Output pixel (x, y) of frame t, pixel centres at integer coordinates:
+ *   1. u = (a00 x + a01 y) + a02, v = (a10 x + a11 y) + a12, in float64, not contracted.
+ *   2. if not (-2 < u < W + 1 and -2 < v < H + 1) - no tap can be inside; NaN included - the pixel is the fill colour 0, 0, 0.  Else
+ *      U = floor(u * 32 + 0.5), x0 = U >> 5, fx = U & 31, and y0, fy from v alike: four taps (x0 + i, y0 + j), i, j in {0, 1}, with the
+ *      weights (32 - fx, fx) x (32 - fy, fy), which sum to 1024.
+ *   3. a tap (xt, yt) outside [0, W) x [0, H) is 0, 0, 0.  An inside tap is the source pixel (flip2 ? W - 1 - xt : xt, yt) taken through
+ *      rule 4 and then rule 5 at (xt, yt).
+ *   4. colour, in integers, in this order; an op with neutral parameters is skipped, so it returns its input bytes:
+ *      a. c'[k] = c[perm[k]] (entries clamped to 0..2; neutral 0, 1, 2).
+ *      b. brightness, V = max(R, G, B): V' = clamp(((V * mq + 128) >> 8) + add, 0, 255), mq = rint(mul * 256) clamped to [0, 65536], add
+ *         to [-255, 255] (neutral 256, 0).  V = 0: R = G = B = V'.  Else every channel c = (2 c V' + V) / (2 V).
+ *      c. hue and saturation, `value` clamped to [-255, 255] (neutral 0; imgaug's AddToHueAndSaturation: a hue turn of value * 360 / 255
+ *         degrees, value added to S on a 0..255 scale), in an HSV with 24576 hue steps per turn:  V = max, C = V - min,
+ *         S = V ? (510 C + V) / (2 V) : 0;  h = 0 if C = 0, else with (base, d) = (0, G - B) if V = R, else (8192, B - R) if V = G, else
+ *         (16384, R - G):  h = (base + ((d + C) * 8192 + C) / (2 C) - 4096) mod 24576.  S' = clamp(S + value, 0, 255),
+ *         C' = (2 V S' + 255) / 510,  h' = (h + floor((value * 49152 + 255) / 510)) mod 24576,  i = h' >> 12, f = h' & 4095,
+ *         p = V - C', q = V - ((C' f + 2048) >> 12), t = V - ((C' (4096 - f) + 2048) >> 12);  (R, G, B) = (V, t, p), (q, V, p),
+ *         (p, V, t), (p, q, V), (t, p, V), (V, p, q) for i = 0 .. 5.  Divisions are of non-negative integers; mod is non-negative.
+ *   5. dropout, mode = column 6: 0 (or anything but 1, 2) none.  1, per pixel: element e = (t H + yt) W + xt.  2, coarse: the cell
+ *      (cy, cx) = ((yt gh) / H, (xt gw) / W) of a gh x gw grid (each clamped to [1, 32768]; nearest-neighbour up-sampling of the
+ *      mask), e = (t gh + cy) gw + cx.  per_channel = 0: all three channels become 0 iff phnet_rng_keep(seed, e, threshold) is false;
+ *      else channel k becomes 0 iff phnet_rng_keep(seed, 3 e + k, threshold) is false.  phnet_rng_keep(seed, idx, thr) =
+ *      (mix64(seed + (idx + 1) * 0x9E3779B97F4A7C15) >> 32) >= thr with the splitmix64 finaliser mix64 (csrc/common.h), all mod 2^64:
+ *      an element is dropped with probability thr / 2^32.
+ *   6. per channel (sum over the taps of weight * tap + 512) >> 10; then q / 255 and (v - mean) / std in f32, layouts as in
+ *      phnet_preprocess_u8.
+ * With the identity matrix one tap has the weight 1024; with neutral colour and no dropout the outputs equal phnet_preprocess_u8's on
+ * the same frames bit for bit.  PHNET_ERR_ARG before any launch: a null pointer (out_u8 excepted), an unknown layout, H or W outside
+ * [1, 32768], H * W * 4 or T * ceil(H W / 256) not below 2^31, a zero std.  T == 0 is a no-op.  Values in the tables cannot be checked
+ * by the entry: the kernel clamps them as stated, so no table makes it read or write out of bounds. */
+int phnet_augment_u8(const uint8_t* frames, float* out, uint8_t* out_u8, const int32_t* flip2, const double* inv, const int32_t* table,
+                     int32_t T, int32_t H, int32_t W, int32_t layout, const float* mean3_host, const float* std3_host, void* stream);
 
 /* ---- lane IoU of the CULane-style evaluator: replaces LaneCompare::get_lane_similarity's two
  * cv::Mat canvases + cv::line + cv::sum (evaluation/culane/src/lane_compare.cpp:11-57).  A lane is a bit mask

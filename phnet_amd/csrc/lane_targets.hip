@@ -5,6 +5,8 @@
 //
 // Rules, per frame (S offsets, R rows, strip_size = img_h / (S - 1), ys = the caller's offsets_ys table, strictly descending):
 //   0. map, per point:  y = y - crop;  flip: x = (src_w - 1) - x;  x = x * scale_x;  y = y * scale_y.
+//   0b. (phnet_lane_targets_aug only; the label half of csrc/augment.hip) in output pixels:  flip2[f]: x = (img_w - 1) - x;  then
+//      (x, y) = ((f00 x + f01 y) + f02, (f10 x + f11 y) + f12) with f = fwd[f], the source -> output matrix.  A null array skips its step.
 //   1. filter:  lanes l < clamp(lanes_num, 0, Lin) with clamp(count, 0, P) > 2 points survive and are numbered in order; lane
 //      number r owns output row r, numbers >= R are ignored, rows without a lane get the default row.
 //   2. default row:  [0] = 1, [1] = 0, everything else -1e5.  A lane with a non-finite mapped coordinate leaves it.
@@ -43,7 +45,7 @@ constexpr float kInvalid = -1e5f;
 constexpr double kPi = 3.141592653589793;
 constexpr double kDblMax = 1.7976931348623157e308;
 
-struct LaneMap { double crop, src_w, scale_x, scale_y; int flip; };
+struct LaneMap { double crop, src_w, scale_x, scale_y; int flip; const int* flip2; const double* fwd; };      // flip2, fwd: rule 0b, or null
 
 __device__ __forceinline__ void write_default(float* __restrict__ row, int W, int lane) {
 #pragma unroll 1
@@ -133,6 +135,15 @@ __device__ __forceinline__ void encode_row(Lds& L, const float* __restrict__ poi
     // ---- rule 0 into LDS; rule 2 ----
     const float* lp = points + ((f * Lin + lsel) * P) * 2;
     bool bad = false;
+    // rule 0b: the frame's matrix goes through lanes 0-5 into vector registers (as scalars its twelve words would not fit beside the
+    // arguments); the pointers are vector values (see the kernel), so the two steps are per-lane selects, not branches
+    const int flip2 = mp.flip2 ? mp.flip2[f] : 0;
+    double m[6];
+    {
+        const double mine = mp.fwd ? mp.fwd[f * 6 + (size_t)min(lane, 5)] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = __shfl(mine, k, 64);
+    }
 #pragma unroll 1
     for (int i = lane; i < n_raw; i += 64) {
         double x = (double)lp[2 * i], y = (double)lp[2 * i + 1];
@@ -140,6 +151,10 @@ __device__ __forceinline__ void encode_row(Lds& L, const float* __restrict__ poi
         if (mp.flip) x = (mp.src_w - 1.0) - x;
         x = x * mp.scale_x;
         y = y * mp.scale_y;
+        x = flip2 ? (img_w - 1.0) - x : x;
+        const double xa = (m[0] * x + m[1] * y) + m[2], ya = (m[3] * x + m[4] * y) + m[5];
+        x = mp.fwd ? xa : x;
+        y = mp.fwd ? ya : y;
         bad |= !(fabs(x) <= kDblMax && fabs(y) <= kDblMax);                        // NaN, +-inf
         L.a[i] = x; L.b[i] = y;
     }
@@ -257,6 +272,9 @@ __global__ __launch_bounds__(64) void lane_targets_kernel(const float* __restric
 {
     __shared__ Lds L;
     const int lane = threadIdx.x, r = blockIdx.y;
+    // the two pointers of rule 0b and the four doubles of rule 0 live in vector registers: held as scalars across the frame loop
+    // beside the other arguments they spill (the values and the arithmetic on them are unchanged)
+    asm volatile("" : "+v"(mp.flip2), "+v"(mp.fwd), "+v"(mp.crop), "+v"(mp.src_w), "+v"(mp.scale_x), "+v"(mp.scale_y));
 #pragma unroll 1
     for (long long f = blockIdx.x; f < F; f += gridDim.x) {
         encode_row(L, points, counts, lanes_num, ys_tab, out + ((size_t)f * R + r) * (size_t)(6 + S), (size_t)f, r, Lin, P, S, img_h,
@@ -272,10 +290,10 @@ static inline bool positive_finite(double v) { return v > 0.0 && v <= kDblMax; }
 // points f32 [F][Lin][P][2] (x, y), counts i32 [F][Lin], lanes_num i32 [F], offsets_ys f64 [S] (device), out f32 [F][R][6+S].
 // 1 <= F < 2^31, 1 <= Lin <= 64, 2 <= P <= 256, 1 <= R <= 64, 2 <= S <= 256; img_h, img_w, strip_size, scale_x, scale_y finite
 // and > 0, crop and src_w finite, flip 0 or 1, all pointers non-null.
-PHNET_API int phnet_lane_targets(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys,
-                                 float* out, int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w,
-                                 double strip_size, double crop, double src_w, double scale_x, double scale_y, int32_t flip,
-                                 void* stream)
+static int launch_lane_targets(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys, float* out,
+                               int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
+                               double crop, double src_w, double scale_x, double scale_y, int32_t flip, const int32_t* flip2,
+                               const double* fwd, void* stream)
 {
     if (!points || !counts || !lanes_num || !offsets_ys || !out) return PHNET_ERR_ARG;
     if (F < 1 || F > 0x7fffffffll || Lin < 1 || Lin > kMaxInLanes || P < 2 || P > kMaxPoints || R < 1 || R > kMaxRows || S < 2 ||
@@ -285,9 +303,29 @@ PHNET_API int phnet_lane_targets(const float* points, const int32_t* counts, con
         !positive_finite(scale_y))
         return PHNET_ERR_ARG;
     if (!(fabs(crop) <= kDblMax) || !(fabs(src_w) <= kDblMax) || (flip != 0 && flip != 1)) return PHNET_ERR_ARG;
-    const LaneMap mp{crop, src_w, scale_x, scale_y, (int)flip};
+    const LaneMap mp{crop, src_w, scale_x, scale_y, (int)flip, flip2, fwd};
     const unsigned gx = (unsigned)(F < kMaxGridX ? F : kMaxGridX);
     hipLaunchKernelGGL(lane_targets_kernel, dim3(gx, (unsigned)R), dim3(64), 0, (hipStream_t)stream, points, counts, lanes_num,
                        offsets_ys, out, (long long)F, (int)Lin, (int)P, (int)R, (int)S, img_h, img_w, strip_size, mp);
     return phnet_launch_status();
+}
+
+PHNET_API int phnet_lane_targets(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys,
+                                 float* out, int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w,
+                                 double strip_size, double crop, double src_w, double scale_x, double scale_y, int32_t flip,
+                                 void* stream)
+{
+    return launch_lane_targets(points, counts, lanes_num, offsets_ys, out, F, Lin, P, R, S, img_h, img_w, strip_size, crop, src_w, scale_x,
+                               scale_y, flip, nullptr, nullptr, stream);
+}
+
+// The same launch with rule 0b: flip2 i32 [F] and fwd f64 [F][6] on the device, each optional (null skips its step; with both null
+// this is phnet_lane_targets).  Their values cannot be checked here; a non-finite product leaves the lane's row the default row.
+PHNET_API int phnet_lane_targets_aug(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys,
+                                     float* out, int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w,
+                                     double strip_size, double crop, double src_w, double scale_x, double scale_y, int32_t flip,
+                                     const int32_t* flip2, const double* fwd, void* stream)
+{
+    return launch_lane_targets(points, counts, lanes_num, offsets_ys, out, F, Lin, P, R, S, img_h, img_w, strip_size, crop, src_w, scale_x,
+                               scale_y, flip, flip2, fwd, stream);
 }

@@ -1109,9 +1109,11 @@ LANE_TARGETS_MAX_ROWS, LANE_TARGETS_MAX_OFFSETS = 64, 256
 
 
 def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: float, img_w: float, strip_size: float,
-                 crop: float = 0.0, src_w: float = 0.0, scale_x: float = 1.0, scale_y: float = 1.0, flip: bool = False, out=None):
+                 crop: float = 0.0, src_w: float = 0.0, scale_x: float = 1.0, scale_y: float = 1.0, flip: bool = False, out=None,
+                 _aug=None):
     """points [F,Lin,P,2], counts i32 [F,Lin], lanes_num i32 [F], offsets_ys f64 [S] (the reference's np.arange table, on the
-    device) -> label rows [F,max_lanes,6+S] by the rules of include/phnet_hip.h.  One launch, no allocation with out=, no sync."""
+    device) -> label rows [F,max_lanes,6+S] by the rules of include/phnet_hip.h.  One launch, no allocation with out=, no sync.
+    (_aug: lane_targets_aug's (flip2, fwd); None is phnet_lane_targets itself.)"""
     _req(points, name="points"); _req(counts, torch.int32, "counts"); _req(lanes_num, torch.int32, "lanes_num")
     _req(offsets_ys, torch.float64, "offsets_ys")
     if points.dim() != 4 or points.shape[-1] != 2 or offsets_ys.dim() != 1:
@@ -1130,9 +1132,65 @@ def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: f
         _req(out, name="out")
         if tuple(out.shape) != (f, r, 6 + s) or out.device != dev:
             raise ValueError(f"lane_targets: out must be {(f, r, 6 + s)} on {dev}, got {tuple(out.shape)} on {out.device}")
-    check(lib().phnet_lane_targets(_ptr(points), _ptr(counts), _ptr(lanes_num), _ptr(offsets_ys), _ptr(out), f, lin, p, r, s, float(img_h),
-                                   float(img_w), float(strip_size), float(crop), float(src_w), float(scale_x), float(scale_y), int(bool(flip)),
-                                   _stream()), "phnet_lane_targets")
+    args = (_ptr(points), _ptr(counts), _ptr(lanes_num), _ptr(offsets_ys), _ptr(out), f, lin, p, r, s, float(img_h), float(img_w),
+            float(strip_size), float(crop), float(src_w), float(scale_x), float(scale_y), int(bool(flip)))
+    if _aug is None:
+        check(lib().phnet_lane_targets(*args, _stream()), "phnet_lane_targets")
+    else:
+        flip2, fwd = _aug
+        if flip2 is not None:
+            _req(flip2, torch.int32, "flip2")
+        if fwd is not None:
+            _req(fwd, torch.float64, "fwd")
+        if (flip2 is not None and (tuple(flip2.shape) != (f,) or flip2.device != dev)) or \
+                (fwd is not None and (tuple(fwd.shape) != (f, 6) or fwd.device != dev)):
+            raise ValueError(f"lane_targets_aug: flip2 i32 [{f}] and fwd f64 [{f},6] on {dev} expected")
+        check(lib().phnet_lane_targets_aug(*args, _ptr(flip2), _ptr(fwd), _stream()), "phnet_lane_targets_aug")
+    return out
+
+
+def lane_targets_aug(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: float, img_w: float, strip_size: float, flip2, fwd,
+                     **kw):
+    """lane_targets behind an augmented image: rule 0b of include/phnet_hip.h with flip2 i32 [F] and fwd f64 [F,6] (the source -> output
+    matrices) on the device; either may be None (its step is skipped).  Keywords as lane_targets."""
+    return lane_targets(points, counts, lanes_num, offsets_ys, max_lanes, img_h, img_w, strip_size, _aug=(flip2, fwd), **kw)
+
+
+AUGMENT_TABLE_COLS, AUGMENT_MAX_SIDE = 16, 32768                  # the i32 table of phnet_augment_u8 (csrc/augment.hip)
+
+
+def augment_u8(frames_u8, flip2, inv, table, mean3, std3, layout: str = "nchw", out=None, out_u8=None):
+    """frames_u8 u8 [T,H,W,3] (resized frames) -> the augmented, normalised clip f32 [T,3,H,W] ("nchw") or [T,H,W,4] ("nhwc4") by the
+    rules of include/phnet_hip.h, with flip2 i32 [T], inv f64 [T,6], table i32 [T,16] on the device and mean3 / std3 ctypes float[3] on
+    the host.  out / out_u8: buffers to write into (out_u8 = None: the 8-bit image is not written).  One launch, no sync."""
+    import ctypes
+    _req(frames_u8, torch.uint8, "frames_u8"); _req(flip2, torch.int32, "flip2"); _req(inv, torch.float64, "inv"); _req(table, torch.int32, "table")
+    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError("augment_u8: frames_u8 [T,H,W,3] expected")
+    if layout not in ("nchw", "nhwc4"):
+        raise ValueError("layout must be 'nchw' or 'nhwc4'")
+    t, h, w, _ = frames_u8.shape
+    dev = frames_u8.device
+    if tuple(flip2.shape) != (t,) or tuple(inv.shape) != (t, 6) or tuple(table.shape) != (t, AUGMENT_TABLE_COLS) or \
+            any(x.device != dev for x in (flip2, inv, table)):
+        raise ValueError(f"augment_u8: flip2 [{t}], inv [{t},6], table [{t},{AUGMENT_TABLE_COLS}] on {dev} expected, got "
+                         f"{tuple(flip2.shape)}, {tuple(inv.shape)}, {tuple(table.shape)}")
+    shape = (t, 3, h, w) if layout == "nchw" else (t, h, w, 4)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        _req(out, name="out")
+        if tuple(out.shape) != shape or out.device != dev:
+            raise ValueError(f"augment_u8: out must be {shape} on {dev}, got {tuple(out.shape)} on {out.device}")
+    if out_u8 is not None:
+        _req(out_u8, torch.uint8, "out_u8")
+        if tuple(out_u8.shape) != (t, h, w, 3) or out_u8.device != dev:
+            raise ValueError(f"augment_u8: out_u8 must be {(t, h, w, 3)} on {dev}")
+        if out_u8.data_ptr() == frames_u8.data_ptr() and t:
+            raise ValueError("augment_u8: out_u8 must not be the input (a warp reads other pixels than it writes)")
+    check(lib().phnet_augment_u8(_ptr(frames_u8), _ptr(out), _ptr(out_u8), _ptr(flip2), _ptr(inv), _ptr(table), t, h, w,
+                                 0 if layout == "nchw" else 1, ctypes.cast(mean3, ctypes.c_void_p), ctypes.cast(std3, ctypes.c_void_p),
+                                 _stream()), "phnet_augment_u8")
     return out
 
 

@@ -5,7 +5,8 @@ Replaces the image half of the reference's per-frame CPU pipeline (libs/dataset/
 transforms.py:150-156 iaa.Resize = cv2 INTER_CUBIC on uint8, datasetOL.py:63-75 ToTensor + Normalize, :11-17 stacking) with ONE
 launch per clip (csrc/preprocess.hip).  The label half (annotated points -> the [max_lanes, 6+S] target rows,
 transforms.py:251-347) is `TargetEncoder` in targets.py beside this file; `TargetEncoder.for_preprocessor(pre, ...)` takes its
-geometry from a ClipPreprocessor.  No CPU path: the frames must already be on the device.
+geometry from a ClipPreprocessor.  Training augmentation (augment.py beside this file) runs behind the resize: `__call__(...,
+augment=params)`.  No CPU path: the frames must already be on the device.
 
 Arithmetic: OpenCV's 8-bit bicubic resize as published (half-pixel centres, a = -0.75 kernel, 11-bit fixed-point taps that
 sum to 2048, replicated borders, rounding 22-bit shift, saturation).  PARITY UNPINNED: cv2 / imgaug are not installed here
@@ -109,6 +110,7 @@ class ClipPreprocessor:
         self.yi, self.yc = torch.from_numpy(yi).to(dev), torch.from_numpy(yc).to(dev)
         self._mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self._std = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self._stage, self._augmenter = {}, None                   # augment=: the resized 8-bit frames per (T, device); the ClipAugmenter
 
     @property
     def frame_shape(self):
@@ -119,9 +121,14 @@ class ClipPreprocessor:
             return (self.surface_rows * 3 // 2, self.pitch)
         return (self.src_h, self.pitch)
 
-    def __call__(self, frames_u8: torch.Tensor, flip: bool = False, layout: str = "nchw", return_u8: bool = False):
+    def __call__(self, frames_u8: torch.Tensor, flip: bool = False, layout: str = "nchw", return_u8: bool = False, augment=None,
+                 out: Optional[torch.Tensor] = None):
         """frames_u8 [T, *frame_shape] uint8 on the device -> float32 [T,3,out_h,out_w] ("nchw", the reference's `img`) or
-        [T,out_h,out_w,4] ("nhwc4", the stem's staging layout); with return_u8 also the resized 8-bit RGB frames."""
+        [T,out_h,out_w,4] ("nhwc4", the stem's staging layout); with return_u8 also the resized 8-bit RGB frames.
+        augment: an AugmentParams (augment.py) of T frames on the device - the resize launch writes the 8-bit frames into a staging
+        buffer this object keeps per T, and the augment launch (phnet_augment_u8) turns them into the result (return_u8: the AUGMENTED
+        8-bit frames); give the same table to TargetEncoder.  out: the float buffer to write into; with it (and, with augment, after one
+        call of the same T) nothing is allocated, so the call can be captured in a graph."""
         if frames_u8.dim() != 1 + len(self.frame_shape) or tuple(frames_u8.shape[1:]) != self.frame_shape:
             raise ValueError(f"frames of {'x'.join(map(str, frames_u8.shape[1:]))}, built for {self.pixel_format} "
                              f"{'x'.join(map(str, self.frame_shape))}")
@@ -131,8 +138,18 @@ class ClipPreprocessor:
         if layout not in ("nchw", "nhwc4"):
             raise ValueError("layout must be 'nchw' or 'nhwc4'")
         t, dev = frames_u8.shape[0], frames_u8.device
-        out = torch.empty((t, 3, self.out_h, self.out_w) if layout == "nchw" else (t, self.out_h, self.out_w, 4), dtype=torch.float32, device=dev)
-        u8 = torch.empty((t, self.out_h, self.out_w, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+        shape = (t, 3, self.out_h, self.out_w) if layout == "nchw" else (t, self.out_h, self.out_w, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"ClipPreprocessor: out must be contiguous float32 {shape} on {dev}")
+        if augment is not None:
+            stage = self._stage.get((t, dev))
+            if stage is None:
+                stage = self._stage[(t, dev)] = torch.empty((t, self.out_h, self.out_w, 3), dtype=torch.uint8, device=dev)
+            u8 = stage
+        else:
+            u8 = torch.empty((t, self.out_h, self.out_w, 3), dtype=torch.uint8, device=dev) if return_u8 else None
         mean, std = ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._std, ctypes.c_void_p)
         if self.pixel_format == "rgb":
             check(lib().phnet_preprocess_u8(frames_u8.data_ptr(), out.data_ptr(), None if u8 is None else u8.data_ptr(),
@@ -148,6 +165,11 @@ class ClipPreprocessor:
                                              0 if layout == "nchw" else 1, _FORMATS[self.pixel_format], rows * pitch, pitch,
                                              self.surface_rows * pitch, ctypes.cast(self._csc, ctypes.c_void_p), mean, std,
                                              torch.cuda.current_stream().cuda_stream), "phnet_preprocess_yuv")
+        if augment is not None:
+            if self._augmenter is None:
+                from phnet_amd.libs.dataset.openlane.augment import ClipAugmenter
+                self._augmenter = ClipAugmenter.for_preprocessor(self)
+            return self._augmenter(u8, augment, layout=layout, out=out, return_u8=return_u8)
         return (out, u8) if return_u8 else out
 
 

@@ -10,7 +10,8 @@ Arithmetic: the reference's float64 path, rule by rule (include/phnet_hip.h), wi
 explicitly (line, parabola, not-a-knot cubic spline).  Pinned to the reference's own executed code on tests/golden/targets_tiny.json.
 PARITY UNPINNED (imgaug is not installed here): the arithmetic of its Resize on line strings - this module uses x * (out_w / src_w)
 and y * (out_h / (src_h - crop)), each ratio formed once in double - and clip_out_of_image_(), which is not built: points outside
-the image are kept (DESIGN.md "Training targets")."""
+the image are kept (DESIGN.md "Training targets").  With `augment=` (augment.py: rule 0b, the flip and the affine of the augmented
+image applied to the points) more points leave the image, so this gap matters more there."""
 from typing import Optional, Sequence
 
 import numpy as np
@@ -51,11 +52,13 @@ class TargetEncoder:
         return cls(pre.out_h, pre.out_w, num_points, max_lanes, src_h=pre.src_h, src_w=pre.src_w, crop_size=pre.crop, device=pre.xi.device)
 
     def __call__(self, points: torch.Tensor, counts: torch.Tensor, lanes_num: torch.Tensor, flip: bool = False,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, augment=None) -> torch.Tensor:
         """points f32 [T,Lin,P,2] in source (camera) pixels, counts i32 [T,Lin], lanes_num i32 [T], all on the device (leading
         dimensions [B,T] are accepted) -> float32 [T,max_lanes,6+S].  flip: the clip was mirrored (datasetOL.py:54-55).
         out: a buffer of that shape to write into, e.g. the `lanes` of a GraphedTrainStep - then nothing is allocated and nothing
-        waits for the device, so the call can be captured in a graph."""
+        waits for the device, so the call can be captured in a graph.
+        augment: the AugmentParams (augment.py) of the same frames, on the device - the labels follow the augmented image
+        (phnet_lane_targets_aug); None is the plain entry, exactly as without the argument."""
         if not (points.is_cuda and counts.is_cuda and lanes_num.is_cuda):
             raise RuntimeError("TargetEncoder: CUDA(HIP) tensors expected; phnet_amd has no CPU path")
         if points.dim() < 4 or points.shape[-1] != 2:
@@ -69,9 +72,16 @@ class TargetEncoder:
         for t, name in ((points, "points"), (counts, "counts"), (lanes_num, "lanes_num"), (out, "out")):
             if t is not None and not t.is_contiguous():
                 raise RuntimeError(f"TargetEncoder: {name} must be contiguous")
-        flat = K.lane_targets(points.view(-1, lin, p, 2), counts.view(-1, lin), lanes_num.view(-1), self.offsets_ys, self.max_lanes,
-                              self.out_h, self.out_w, self.strip_size, crop=self.crop, src_w=self.src_w, scale_x=self.scale_x,
-                              scale_y=self.scale_y, flip=flip, out=None if out is None else out.view(-1, self.max_lanes, 6 + self.num_points))
+        kw = dict(crop=self.crop, src_w=self.src_w, scale_x=self.scale_x, scale_y=self.scale_y, flip=flip,
+                  out=None if out is None else out.view(-1, self.max_lanes, 6 + self.num_points))
+        args = (points.view(-1, lin, p, 2), counts.view(-1, lin), lanes_num.view(-1), self.offsets_ys, self.max_lanes, self.out_h, self.out_w,
+                self.strip_size)
+        if augment is None:
+            flat = K.lane_targets(*args, **kw)
+        else:
+            if len(augment) != args[2].shape[0] or augment.device != points.device:
+                raise ValueError(f"TargetEncoder: an AugmentParams of {args[2].shape[0]} frames on {points.device} expected")
+            flat = K.lane_targets_aug(*args, augment.flip2, augment.fwd, **kw)
         return flat.view(shape) if out is None else out
 
 
