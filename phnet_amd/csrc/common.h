@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 #define PHNET_OK 0
 #define PHNET_ERR_ARG (-1)        // bad shape / null pointer / unsupported size
@@ -12,6 +13,15 @@
 
 static inline int phnet_launch_status() {
     return hipGetLastError() == hipSuccess ? PHNET_OK : PHNET_ERR_LAUNCH;
+}
+
+// Lets the kernels `fns` take up to `bytes` of dynamic LDS (above the 64 KB a launch gets unasked).  A launch site calls it once:
+//   static bool attr = false;
+//   if (!attr && !(attr = phnet_allow_dynamic_lds({(const void*)kernel, ...}, bytes))) return PHNET_ERR_LAUNCH;
+static inline bool phnet_allow_dynamic_lds(std::initializer_list<const void*> fns, int bytes) {
+    for (const void* f : fns)
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    return true;
 }
 
 // Wave-wide reductions on the DPP data path (quad swaps, row rotations, row broadcasts - the rocPRIM sequence): six

@@ -1,4 +1,4 @@
-// fp32 MFMA implicit-GEMM building blocks for gfx950 (CDNA4), shared by conv.hip and gemm.hip.
+// fp32 MFMA implicit-GEMM building blocks for gfx950 (CDNA4), shared by every GEMM source (conv*.hip, linear_bwd.hip, wgrad*.hip).
 //
 // Arithmetic: v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: bit-for-bit an fmaf chain; dense peak
 // 157.3 TF/s = 64 FLOP/clk/SIMD).  The reference runs this path in fp32 end to end
@@ -67,7 +67,7 @@ __device__ __forceinline__ void mma_step(const float (&a)[FM][8], const float (&
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
 }
 
-// ---- split-bf16 arithmetic (MMA = 1, opt-in through phnet_tune_mma; the product default stays f32-input MFMA) --------
+// ---- split-bf16 arithmetic (MMA = 1, opt-in through phnet_tune_mma; the product default is mode 3 below) --------
 // Every f32 operand is split in registers into two bf16 terms x = hi + lo (hi = bf16(x), lo = bf16(x - hi): 16 mantissa
 // bits) and a product becomes hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with f32 accumulation (the dropped
 // lo*lo term and the split residual are ~2^-16 relative per product).  The fragment registers are the SAME as for the

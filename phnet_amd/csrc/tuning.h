@@ -4,7 +4,7 @@
 #pragma once
 
 struct Tuning {
-    // ---- arithmetic and operand path of the GEMM kernels (conv.hip) ----
+    // ---- arithmetic and operand path of the GEMM kernels (conv.hip, conv_wgrad.hip, linear_bwd.hip) ----
     int mma_mode = 3;            // 3: exact 3-term bf16 split at staging; 0: f32-input MFMA; 1 / 2: bf16 splits in registers (phnet_tune_mma)
     int pf = 4;                  // register prefetch depth in K tiles (phnet_tune_mma sets 4 in mode 3, else 1; phnet_tune_force_k_tile(-101 / -102 / -104))
     int buf_loads = 1;           // buffer-load operand path where it applies (phnet_tune_force_k_tile(-200 / -201))
@@ -14,7 +14,7 @@ struct Tuning {
     // ---- forced forward / dgrad plan (0 = heuristic) ----
     int force_bm = 0, force_bn = 0, force_splits = 0;       // phnet_tune_force_conv_tile
     int force_kt = 0;                                       // phnet_tune_force_k_tile(16 | 32 | 64)
-    // ---- weight gradient (conv.hip; phnet_tune_wgrad: bits of its first argument, workgroup targets in its second) ----
+    // ---- weight gradient (conv_wgrad.hip; phnet_tune_wgrad: bits of its first argument, workgroup targets in its second) ----
     int wgrad_bm128 = 1;         // bit 0: 128-row tiles of the generic kernel where they win
     int wgrad_smallp = 1;        // bit 1 switches the few-rows Linear kernels (weight gradient and fused backward) off
     int wgrad_bkw = 16;          // bit 2: 32 pixels per K step of the generic kernel in mode 3

@@ -12,7 +12,7 @@
 // The bias gradient is summed by the producers of the first column tile on the dY blocks they stage anyway.
 #include <type_traits>
 #include "igemm.h"
-#include "wgrad3s.h"
+#include "wgrad_pc.h"
 
 using namespace igemm;
 
@@ -183,11 +183,7 @@ int phnet_wgrad1s_kstep() { return L_BKW; }
 int phnet_wgrad1s_launch(const float* dy, const float* x, float* out, float* dbias, Wgrad1sShape g, int accumulate, hipStream_t st)
 {
     static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)wgrad1s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L_BYTES) != hipSuccess)
-            return PHNET_ERR_LAUNCH;
-        attr = true;
-    }
+    if (!attr && !(attr = phnet_allow_dynamic_lds({(const void*)wgrad1s_kernel}, L_BYTES))) return PHNET_ERR_LAUNCH;
     dim3 grid((unsigned)((g.Co / 128) * (g.Ci / 128)), 1, (unsigned)g.splits);
     hipLaunchKernelGGL(wgrad1s_kernel, grid, dim3(L_NT), L_BYTES, st, dy, x, out, dbias, g, dbias != nullptr, accumulate);
     return phnet_launch_status();

@@ -2,7 +2,7 @@
 //
 //   dW[co][ky][kx][ci] = sum over pixels p of dY[p][co] * X[p + (ky-1) W + (kx-1)][ci]          (libs/models/resnet.py:79-95 backward)
 //
-// Same tile program as conv_wgrad3x3_kernel (conv.hip): one workgroup = (64 co) x (64 ci) x (the three taps of filter row ky),
+// Same tile program as conv_wgrad3x3_kernel (conv_wgrad.hip; the shared pieces: wgrad3_taps.h): one workgroup = (64 co) x (64 ci) x (the three taps of filter row ky),
 // per K step it stages dY[16 px][64 co] and X[18 px][64 ci] as three bf16 planes each (x = hi + mid + lo exactly) and twelve
 // wavefronts - tap group dx = wave / 4, quadrant wave % 4 - multiply 32x32 blocks out of them with transposed LDS reads.
 //
@@ -30,7 +30,8 @@
 // x = W-1 for dx = +1: at most one per 16-pixel block, W >= 16) is cleared in the dY fragment of that tap group.
 #include <type_traits>
 #include "igemm.h"
-#include "wgrad3s.h"
+#include "wgrad3_taps.h"
+#include "wgrad_pc.h"
 
 using namespace igemm;
 
@@ -40,14 +41,11 @@ constexpr int S_NT = 1024, S_CONSUMERS = 12;                 // 12 consumer + 4 
 constexpr int S_PF = 4;                                      // producer register ring: K steps in flight per thread (what bounds the step is
                                                              // load latency / steps in flight: 4 -> 8 steps, see wgrad3s_kernel)
 
-template <int NSUB> struct S3Lds {
+template <int NSUB> struct S3Lds : Wgrad3Image<BK * NSUB> {
     static constexpr int BKW = BK * NSUB;                    // pixels per K step
-    static constexpr int ROWS = BKW + 2;                     // X rows of a step: pixels pt-1 .. pt+BKW of the shifted image row
-    static constexpr int PITCH = KStridedPlanes<64, BK>::PITCH;      // 192 bytes: 64 bf16 + pad (igemm.h)
-    static constexpr int PLANE = ROWS * PITCH, IMG = 3 * PLANE;      // both operands use the ROWS-row image (dY leaves two rows unused)
-    static constexpr int STAGE = 2 * IMG;                    // dY image | X image
+    static constexpr int STAGE = 2 * Wgrad3Image<BKW>::IMG;  // dY image | X image
     static constexpr int DUMP = 3 * STAGE;                   // where the idle lanes of the halo wave store
-    static constexpr int BYTES = 3 * STAGE + 2 * PLANE + 512;
+    static constexpr int BYTES = 3 * STAGE + 2 * Wgrad3Image<BKW>::PLANE + 512;
 };
 
 template <int NSUB>
@@ -60,10 +58,8 @@ __global__ __launch_bounds__(S_NT) void wgrad3s_kernel(const float* __restrict__
 
     const int NC = 9 * g.Ci, W = g.W, HW = g.H * g.W;
     const int P = g.N * HW;
-    const int ctiles = g.Ci >> 6;
-    const unsigned tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int dyi = (int)(tile % 3), ct = (int)((tile / 3) % ctiles), mt = (int)(tile / (3 * ctiles));
-    const int m0 = mt * 64, c0 = ct * 64, dy = dyi - 1;
+    const Wgrad3Tile t3 = wgrad3_tile(blockIdx.x, gridDim.x, g.Ci);
+    const int m0 = t3.m0, c0 = t3.c0, dy = t3.dy;
     const int p_begin = blockIdx.z * g.pix_per_split, p_end = min(P, p_begin + g.pix_per_split);
     const int nsteps = p_begin < p_end ? (p_end - p_begin + BKW - 1) / BKW : 0;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -158,41 +154,21 @@ __global__ __launch_bounds__(S_NT) void wgrad3s_kernel(const float* __restrict__
     }
 
     // ======================================= consumers: fragments -> MFMAs =======================================
-    const int tg = wave >> 2, dx = tg - 1;                   // tap group of this wave
-    const int wm = ((wave >> 1) & 1) * 32, wn = (wave & 1) * 32;
+    const Wgrad3Wave w3 = wgrad3_wave(wave);
+    const int dx = w3.dx, wm = w3.wm, wn = w3.wn;
     const bool from_old = g.splits == 1 && accumulate;
-    const int n_base = (dyi * 3 + tg) * g.Ci + c0 + wn;      // first column of this wave's block in [Co][9 Ci]
+    const int n_base = wgrad3_n_base(t3, w3, g.Ci);
     f32x16 acc[1][1];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int n = n_base + frag_col(lane), m = m0 + wm + frag_row(lane, e);
-        const float v = out[from_old ? (size_t)m * NC + n : 0];
-        acc[0][0][e] = from_old ? v : 0.f;
-    }
+    for (int e = 0; e < 16; ++e) acc[0][0][e] = wgrad3_acc_start(out, from_old, m0 + wm, n_base, NC, lane, e);
     if (nsteps > 0) {
         Frag3 fa[2], fb[2];
         const unsigned char* a_src = lds_raw + wm * 2;
         const unsigned char* b_src = lds_raw + IMG + (dx + 1) * PITCH + wn * 2;
         auto read_frags = [&](int stage_off, int ks, Frag3& a, Frag3& b) {
-            Frag3 (&a1)[1] = *reinterpret_cast<Frag3 (*)[1]>(&a);
-            Frag3 (&b1)[1] = *reinterpret_cast<Frag3 (*)[1]>(&b);
-            read_kstrided3<1, PITCH, PLANE>(a_src + stage_off, lane, ks, a1);
-            read_kstrided3<1, PITCH, PLANE>(b_src + stage_off, lane, ks, b1);
+            wgrad3_read_frags<PITCH, PLANE>(a_src + stage_off, b_src + stage_off, lane, ks, a, b);
         };
         const int h8 = (lane >> 5) * 8;
-        // clears, in a dY fragment, pixel ke of its 16-pixel block (this lane holds k = h8 .. h8 + 7)
-        auto mask_edge = [&](Frag3& a, int ke) {
-            const int j = ke - h8;
-            const int ji = j >> 1;                            // register of the element (other half wave: none)
-            const unsigned wmask = (j & 1) ? 0x0000ffffu : 0xffff0000u;
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            u32x4 m;
-            m.x = ji == 0 ? wmask : 0xffffffffu; m.y = ji == 1 ? wmask : 0xffffffffu;
-            m.z = ji == 2 ? wmask : 0xffffffffu; m.w = ji == 3 ? wmask : 0xffffffffu;
-            a.hi = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a.hi) & m);
-            a.mid = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a.mid) & m);
-            a.lo = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a.lo) & m);
-        };
         int mx = p_begin % W;                                // image column of the first pixel of the sub-step whose fragment is masked next
         int o_cur = 0, o_nxt = STAGE;
         __syncthreads();                                     // steps 0 and 1 are staged
@@ -205,8 +181,8 @@ __global__ __launch_bounds__(S_NT) void wgrad3s_kernel(const float* __restrict__
                 if (ks + 1 < NSUB) read_frags(o_cur, ks + 1, fa[nxt], fb[nxt]);
                 else read_frags(o_nxt, 0, fa[nxt], fb[nxt]);
                 {
-                    const int ke = dx < 0 ? (mx == 0 ? 0 : W - mx) : W - 1 - mx;
-                    if (dx != 0 && ke < BK) mask_edge(fa[cur], ke);
+                    const int ke = dx < 0 ? (mx == 0 ? 0 : W - mx) : W - 1 - mx;              // read, then mask: the order conv_wgrad3x3_kernel turns round
+                    if (dx != 0 && ke < BK) wgrad3_mask_edge(fa[cur], ke, h8);
                     mx += BK;
                     mx -= mx >= W ? W : 0;
                 }
@@ -225,11 +201,7 @@ __global__ __launch_bounds__(S_NT) void wgrad3s_kernel(const float* __restrict__
         }
         if (t < nsteps) step(std::integral_constant<int, 0>{});
     }
-    const bool direct = g.splits == 1;
-    float* dst = direct ? out : out + (size_t)blockIdx.z * ((size_t)g.Co * NC + g.Co);
-#pragma unroll
-    for (int e = 0; e < 16; ++e)
-        dst[(size_t)(m0 + wm + frag_row(lane, e)) * NC + n_base + frag_col(lane)] = acc[0][0][e];
+    wgrad3_store(out, g.splits, blockIdx.z, g.Co, NC, m0 + wm, n_base, lane, acc[0][0]);
 }
 
 constexpr int S_NSUB = 2;
@@ -241,11 +213,7 @@ int phnet_wgrad3s_kstep() { return BK * S_NSUB; }
 int phnet_wgrad3s_launch(const float* dy, const float* x, float* out, Wgrad3sShape g, int accumulate, hipStream_t st)
 {
     static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)wgrad3s_kernel<S_NSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, S3Lds<S_NSUB>::BYTES) != hipSuccess)
-            return PHNET_ERR_LAUNCH;
-        attr = true;
-    }
+    if (!attr && !(attr = phnet_allow_dynamic_lds({(const void*)wgrad3s_kernel<S_NSUB>}, S3Lds<S_NSUB>::BYTES))) return PHNET_ERR_LAUNCH;
     dim3 grid((unsigned)((g.Co / 64) * (g.Ci / 64) * 3), 1, (unsigned)g.splits);
     hipLaunchKernelGGL((wgrad3s_kernel<S_NSUB>), grid, dim3(S_NT), S3Lds<S_NSUB>::BYTES, st, dy, x, out, g, accumulate);
     return phnet_launch_status();

@@ -1,4 +1,5 @@
-// Internal (not part of the C-ABI): launch of the producer / consumer weight-gradient kernel of csrc/wgrad3s.hip.
+// Internal (not part of the C-ABI): launches of the two producer / consumer weight-gradient kernels, called by csrc/conv_wgrad.hip.
+// ---- csrc/wgrad3s.hip: 3x3 / stride 1 / pad 1, the three taps of a filter row per workgroup ----
 #pragma once
 #include "common.h"
 

@@ -132,7 +132,7 @@ def query_args(lib, op: str, shape) -> dict:
 # csrc/conv.hip launch_conv:       ksteps = ceil(K / k_tile),  k_per_split = ceil(ksteps / splits) * k_tile
 #                                  conv3x3s1_kernel: units = 3 * (A-side channels / 16), k_per_split = ceil(units / splits)
 # csrc/conv3p.hip p3_plan:         units = 3 * (Ca / 16),  units_per_split = ceil(units / splits)
-# csrc/conv.hip phnet_conv2d_wgrad: steps = ceil(P / pixels per step),  pix_per_split = ceil(steps / splits) * pixels per step
+# csrc/conv_wgrad.hip phnet_conv2d_wgrad: steps = ceil(P / pixels per step),  pix_per_split = ceil(steps / splits) * pixels per step
 WGRAD_PIXELS_PER_STEP = {W3S: 32, W3: 16, W1S: 16, WG64: 16, WG128: 16}
 
 
