@@ -294,8 +294,8 @@ int phnet_preprocess_yuv(const uint8_t* frames, float* out, uint8_t* out_u8,
 /* ---- training augmentation of a clip (csrc/augment.hip): the point-wise ops and the affine of the reference's imgaug pipeline
  * (transforms.py:190-249: HorizontalFlip, ChannelShuffle, MultiplyAndAddToBrightness, AddToHueAndSaturation, Dropout / CoarseDropout,
  * Affine with mode = 'constant', cval = 0) on the RESIZED 8-bit image, in the reference's order with the affine last, in one launch and
- * without an intermediate image; its blurs and edge filters are not built.  PARITY UNPINNED against imgaug / cv2 (DESIGN.md "Training
- * augmentation"): the rules below are the definition.
+ * without an intermediate image; its blurs and edge filters are rule 7, behind phnet_augment_stencil_u8 below.  PARITY UNPINNED against
+ * imgaug / cv2 (DESIGN.md "Training augmentation"): the rules below are the definition.
  * frames u8 [T][H][W][3] on the device (the out_u8 of phnet_preprocess_u8 / _yuv); out f32 NCHW [T][3][H][W] (layout 0) or NHWC4
  * [T][H][W][4] (layout 1); out_u8 optional [T][H][W][3], the augmented 8-bit image; mean3 / std3 HOST pointers.  Per-frame parameters,
  * all on the device and read by the kernel (a replayed graph sees what they hold then): flip2 i32 [T]; inv f64 [T][6], the
@@ -333,6 +333,41 @@ int phnet_preprocess_yuv(const uint8_t* frames, float* out, uint8_t* out_u8,
  * by the entry: the kernel clamps them as stated, so no table makes it read or write out of bounds. */
 int phnet_augment_u8(const uint8_t* frames, float* out, uint8_t* out_u8, const int32_t* flip2, const double* inv, const int32_t* table,
                      int32_t T, int32_t H, int32_t W, int32_t layout, const float* mean3_host, const float* std3_host, void* stream);
+
+/* phnet_augment_u8 with the neighbourhood ops of the reference's 'complex' recipe (transforms.py:220-238: EdgeDetect / DirectedEdgeDetect
+ * between the hue change and the dropout, MotionBlur / MedianBlur / GaussianBlur between the dropout and the affine), csrc/
+ * augment_stencil.hip.  PARITY UNPINNED against imgaug / cv2 like rules 1-6: rule 7 is the definition; op order, borders and the meaning
+ * of the parameters follow imgaug's and OpenCV's documentation - filter2D and GaussianBlur with BORDER_REFLECT_101, medianBlur with
+ * BORDER_REPLICATE, OpenCV's defaults for the calls imgaug makes, written down from memory.
+ * The arguments of phnet_augment_u8, and: stencil i32 [T][40] on the device, read by the kernels like the other tables, with columns
+ * 0 edge filter on (non-zero), 1-9 the edge weights e row-major, 10 blur kind, 11 k, 12-36 the first k * k entries m row-major (kind 1)
+ * or the first k entries g (kind 3), 37-39 zero; staged u8 [T][H][W][3], scratch on the device that the caller owns, neither `frames`
+ * nor `out_u8`.
+ *   7. All coordinates are those of the flipped source image, the (xt, yt) of rule 3.
+ *      r(i, n), reflect-101: 0 if n = 1; else with p = 2 (n - 1) and i' = i mod p (non-negative): i' if i' < n, else p - i'.  Defined
+ *      for every i, so an image may be smaller than a radius.
+ *      C(x, y): rule 4 on the source pixel (flip2 ? W - 1 - x : x, y).
+ *      E(x, y): C(x, y) with the edge filter off.  On, per channel: clamp((sum over dy, dx in {-1, 0, 1} of e[dy + 1][dx + 1] *
+ *      C(r(x + dx, W), r(y + dy, H)) + 2048) >> 12, 0, 255), e signed Q12, each weight clamped to [-65536, 65536], >> arithmetic.
+ *      D(x, y): rule 5 at (x, y) applied to E(x, y), with the element indices of rule 5.
+ *      B(x, y), by the blur kind; k is clamped to [3, 5] (kinds 1, 2) or [3, 9] (kind 3) and an even k is raised by one, R = k / 2:
+ *        0, and every kind but 1, 2, 3: D(x, y).
+ *        1, a k x k convolution (motion blur): clamp((sum over j, i in [0, k) of m[j][i] * D(r(x + i - R, W), r(y + j - R, H)) + 2048)
+ *           >> 12, 0, 255), m Q12, each weight clamped to [0, 65536].
+ *        2, a k x k median: per channel the median of the k * k values D(clamp(x + i - R, 0, W - 1), clamp(y + j - R, 0, H - 1)).
+ *        3, a separable Gaussian: clamp((sum over j of g[j] * (sum over i of g[i] * D(r(x + i - R, W), r(y + j - R, H))) + 32768) >> 16,
+ *           0, 255), g Q8, each weight clamped to [0, 256]; nothing is rounded between the two passes.
+ *      Rule 3 then reads: an inside tap (xt, yt) is B(xt, yt).  For a frame with the edge filter off and blur kind 0 that is rule 3 as it
+ *      stands above, and the frame's bytes are phnet_augment_u8's.
+ * Two launches: the staging launch writes B of every frame that has the edge filter on or a blur kind 1-3 into `staged` (workgroups of
+ * the other frames return at once: the launch is the same whatever the table holds, so a captured graph stays valid), the image launch
+ * reads the taps of those frames from `staged` and runs rules 4, 5 itself on the others.  stencil == NULL is phnet_augment_u8, one launch
+ * and bit for bit; so is an all-zero stencil table.  PHNET_ERR_ARG as phnet_augment_u8, and: a null `staged` with a non-null stencil,
+ * T * ceil(W / 64) * ceil(H / 16) not below 2^31.  The kernels clamp what they read from the table as stated: no table contents make
+ * them read or write out of bounds. */
+int phnet_augment_stencil_u8(const uint8_t* frames, float* out, uint8_t* out_u8, const int32_t* flip2, const double* inv,
+                             const int32_t* table, const int32_t* stencil, uint8_t* staged, int32_t T, int32_t H, int32_t W, int32_t layout,
+                             const float* mean3_host, const float* std3_host, void* stream);
 
 /* ---- lane IoU of the CULane-style evaluator: replaces LaneCompare::get_lane_similarity's two
  * cv::Mat canvases + cv::line + cv::sum (evaluation/culane/src/lane_compare.cpp:11-57).  A lane is a bit mask

@@ -1159,10 +1159,15 @@ def lane_targets_aug(points, counts, lanes_num, offsets_ys, max_lanes: int, img_
 AUGMENT_TABLE_COLS, AUGMENT_MAX_SIDE = 16, 32768                  # the i32 table of phnet_augment_u8 (csrc/augment.hip)
 
 
-def augment_u8(frames_u8, flip2, inv, table, mean3, std3, layout: str = "nchw", out=None, out_u8=None):
+AUGMENT_STENCIL_COLS = 40                                         # the i32 stencil table of phnet_augment_stencil_u8 (csrc/augment_stencil.hip)
+
+
+def augment_u8(frames_u8, flip2, inv, table, mean3, std3, layout: str = "nchw", out=None, out_u8=None, stencil=None, staged=None):
     """frames_u8 u8 [T,H,W,3] (resized frames) -> the augmented, normalised clip f32 [T,3,H,W] ("nchw") or [T,H,W,4] ("nhwc4") by the
     rules of include/phnet_hip.h, with flip2 i32 [T], inv f64 [T,6], table i32 [T,16] on the device and mean3 / std3 ctypes float[3] on
-    the host.  out / out_u8: buffers to write into (out_u8 = None: the 8-bit image is not written).  One launch, no sync."""
+    the host.  out / out_u8: buffers to write into (out_u8 = None: the 8-bit image is not written).  One launch, no sync.
+    stencil: i32 [T,40] on the device, the neighbourhood ops of rule 7 - then phnet_augment_stencil_u8 runs (two launches) and staged,
+    a u8 [T,H,W,3] scratch buffer on the device that is neither the input nor out_u8, is required."""
     import ctypes
     _req(frames_u8, torch.uint8, "frames_u8"); _req(flip2, torch.int32, "flip2"); _req(inv, torch.float64, "inv"); _req(table, torch.int32, "table")
     if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
@@ -1188,9 +1193,24 @@ def augment_u8(frames_u8, flip2, inv, table, mean3, std3, layout: str = "nchw", 
             raise ValueError(f"augment_u8: out_u8 must be {(t, h, w, 3)} on {dev}")
         if out_u8.data_ptr() == frames_u8.data_ptr() and t:
             raise ValueError("augment_u8: out_u8 must not be the input (a warp reads other pixels than it writes)")
-    check(lib().phnet_augment_u8(_ptr(frames_u8), _ptr(out), _ptr(out_u8), _ptr(flip2), _ptr(inv), _ptr(table), t, h, w,
-                                 0 if layout == "nchw" else 1, ctypes.cast(mean3, ctypes.c_void_p), ctypes.cast(std3, ctypes.c_void_p),
-                                 _stream()), "phnet_augment_u8")
+    mean_p, std_p = ctypes.cast(mean3, ctypes.c_void_p), ctypes.cast(std3, ctypes.c_void_p)
+    if stencil is None:
+        check(lib().phnet_augment_u8(_ptr(frames_u8), _ptr(out), _ptr(out_u8), _ptr(flip2), _ptr(inv), _ptr(table), t, h, w,
+                                     0 if layout == "nchw" else 1, mean_p, std_p, _stream()), "phnet_augment_u8")
+        return out
+    _req(stencil, torch.int32, "stencil")
+    if tuple(stencil.shape) != (t, AUGMENT_STENCIL_COLS) or stencil.device != dev:
+        raise ValueError(f"augment_u8: stencil must be [{t},{AUGMENT_STENCIL_COLS}] on {dev}, got {tuple(stencil.shape)}")
+    if staged is None:
+        raise ValueError("augment_u8: a stencil table needs a staged buffer")
+    _req(staged, torch.uint8, "staged")
+    if tuple(staged.shape) != (t, h, w, 3) or staged.device != dev:
+        raise ValueError(f"augment_u8: staged must be {(t, h, w, 3)} on {dev}")
+    if t and (staged.data_ptr() == frames_u8.data_ptr() or (out_u8 is not None and staged.data_ptr() == out_u8.data_ptr())):
+        raise ValueError("augment_u8: staged must be neither the input nor out_u8 (both launches read other pixels than they write)")
+    check(lib().phnet_augment_stencil_u8(_ptr(frames_u8), _ptr(out), _ptr(out_u8), _ptr(flip2), _ptr(inv), _ptr(table), _ptr(stencil),
+                                         _ptr(staged), t, h, w, 0 if layout == "nchw" else 1, mean_p, std_p, _stream()),
+          "phnet_augment_stencil_u8")
     return out
 
 

@@ -126,7 +126,8 @@ class ClipPreprocessor:
         """frames_u8 [T, *frame_shape] uint8 on the device -> float32 [T,3,out_h,out_w] ("nchw", the reference's `img`) or
         [T,out_h,out_w,4] ("nhwc4", the stem's staging layout); with return_u8 also the resized 8-bit RGB frames.
         augment: an AugmentParams (augment.py) of T frames on the device - the resize launch writes the 8-bit frames into a staging
-        buffer this object keeps per T, and the augment launch (phnet_augment_u8) turns them into the result (return_u8: the AUGMENTED
+        buffer this object keeps per T, and the augment launch (phnet_augment_u8; with a stencil table in the params
+        phnet_augment_stencil_u8, whose own staging buffer the ClipAugmenter keeps per T) turns them into the result (return_u8: the AUGMENTED
         8-bit frames); give the same table to TargetEncoder.  out: the float buffer to write into; with it (and, with augment, after one
         call of the same T) nothing is allocated, so the call can be captured in a graph."""
         if frames_u8.dim() != 1 + len(self.frame_shape) or tuple(frames_u8.shape[1:]) != self.frame_shape:
