@@ -130,6 +130,30 @@ int phnet_lane_targets_aug(const float* points, const int32_t* counts, const int
                            int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
                            double crop, double src_w, double scale_x, double scale_y, int32_t flip, const int32_t* flip2,
                            const double* fwd, void* stream);
+/* The same launch with the reference's clip_out_of_image_() (transforms.py:68) between the map and the filter, and the number of
+ * fragments it leaves per frame.  One rule more, on the mapped points in INPUT order, after rules 0 / 0b and before rule 1, in
+ * float64, not contracted:
+ *   0c. (clip = 1) rectangle: Wc = img_w - 1e-3, Hc = img_h - 1e-3; a point is in iff 0 <= x <= Wc and 0 <= y <= Hc (false for NaN).
+ *       A lane with a non-finite mapped coordinate is not clipped: it is ONE fragment with all its points (rule 2 keeps its row the
+ *       default row, as before).  For a finite lane of n points every maximal run of consecutive in-points p_a .. p_b gives one
+ *       fragment [E] p_a .. p_b [X]: E exists iff a > 0 and is the crossing of the segment p_a -> p_(a-1); X exists iff b < n - 1 and
+ *       is the crossing of p_b -> p_(b+1).  A crossing is computed from the in endpoint q towards the out endpoint o: for each
+ *       coordinate c whose bound o violates (the bound is 0, Wc or Hc), t_c = (bound - q_c) / (o_c - q_c); t is the smaller of the
+ *       two, an unviolated coordinate does not take part; the point is q + t * (o - q), and the coordinate(s) that gave t are set
+ *       to the bound itself (on a tie both: a corner).  A crossing equal to q in both coordinates is dropped.  A segment with
+ *       BOTH ends out is never clipped, even where it crosses the image: its two-point fragment would fall to rule 1, so it is not
+ *       produced.
+ *   1 on fragments: fragments of more than 2 points survive and are numbered in order of (input lane, run); number r owns row r;
+ *       numbers >= R are ignored.  Everything from rule 2 on is unchanged, with the fragment's points [E] p_a .. p_b [X] in that
+ *       order as the lane's input order.
+ * A frame with no point outside the rectangle encodes exactly as without the rule; with clip = 0 this is phnet_lane_targets_aug, bit
+ * for bit.  frag_count i32 [F] on the device, or null: the surviving fragments of the frame BEFORE the R cap (with clip = 0: the
+ * surviving lanes), written on every call.  flip2 and fwd as above.  Limits as above, and clip 0 or 1, and 2 <= P <= 254 with
+ * clip = 1 (a fragment has up to P + 2 points, and the staging holds 256). */
+int phnet_lane_targets_clip(const float* points, const int32_t* counts, const int32_t* lanes_num, const double* offsets_ys, float* out,
+                            int64_t F, int32_t Lin, int32_t P, int32_t R, int32_t S, double img_h, double img_w, double strip_size,
+                            double crop, double src_w, double scale_x, double scale_y, int32_t flip, const int32_t* flip2,
+                            const double* fwd, int32_t clip, int32_t* frag_count, void* stream);
 
 /* ---- lane-anchor ROI pooling: replaces F.grid_sample(..., align_corners=True) + permutes
  * (libs/models/Router4OL.py:132-150, 269-272) and its backward (ATen grid_sampler_2d_backward).

@@ -1106,14 +1106,15 @@ def lane_track(kept_rows, num, state, thr: float, max_age: int, out=None):
 
 LANE_TARGETS_MAX_IN_LANES, LANE_TARGETS_MAX_POINTS = 64, 256       # limits of phnet_lane_targets (csrc/lane_targets.hip)
 LANE_TARGETS_MAX_ROWS, LANE_TARGETS_MAX_OFFSETS = 64, 256
+LANE_TARGETS_MAX_POINTS_CLIP = 254                                # with rule 0c: a fragment has up to P + 2 points
 
 
 def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: float, img_w: float, strip_size: float,
                  crop: float = 0.0, src_w: float = 0.0, scale_x: float = 1.0, scale_y: float = 1.0, flip: bool = False, out=None,
-                 _aug=None):
+                 _aug=None, _clip=None):
     """points [F,Lin,P,2], counts i32 [F,Lin], lanes_num i32 [F], offsets_ys f64 [S] (the reference's np.arange table, on the
     device) -> label rows [F,max_lanes,6+S] by the rules of include/phnet_hip.h.  One launch, no allocation with out=, no sync.
-    (_aug: lane_targets_aug's (flip2, fwd); None is phnet_lane_targets itself.)"""
+    (_aug: lane_targets_aug's (flip2, fwd); None is phnet_lane_targets itself.  _clip: lane_targets_clip's (clip, frag_count).)"""
     _req(points, name="points"); _req(counts, torch.int32, "counts"); _req(lanes_num, torch.int32, "lanes_num")
     _req(offsets_ys, torch.float64, "offsets_ys")
     if points.dim() != 4 or points.shape[-1] != 2 or offsets_ys.dim() != 1:
@@ -1134,10 +1135,10 @@ def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: f
             raise ValueError(f"lane_targets: out must be {(f, r, 6 + s)} on {dev}, got {tuple(out.shape)} on {out.device}")
     args = (_ptr(points), _ptr(counts), _ptr(lanes_num), _ptr(offsets_ys), _ptr(out), f, lin, p, r, s, float(img_h), float(img_w),
             float(strip_size), float(crop), float(src_w), float(scale_x), float(scale_y), int(bool(flip)))
-    if _aug is None:
+    if _aug is None and _clip is None:
         check(lib().phnet_lane_targets(*args, _stream()), "phnet_lane_targets")
     else:
-        flip2, fwd = _aug
+        flip2, fwd = _aug if _aug is not None else (None, None)
         if flip2 is not None:
             _req(flip2, torch.int32, "flip2")
         if fwd is not None:
@@ -1145,7 +1146,18 @@ def lane_targets(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: f
         if (flip2 is not None and (tuple(flip2.shape) != (f,) or flip2.device != dev)) or \
                 (fwd is not None and (tuple(fwd.shape) != (f, 6) or fwd.device != dev)):
             raise ValueError(f"lane_targets_aug: flip2 i32 [{f}] and fwd f64 [{f},6] on {dev} expected")
-        check(lib().phnet_lane_targets_aug(*args, _ptr(flip2), _ptr(fwd), _stream()), "phnet_lane_targets_aug")
+        if _clip is None:
+            check(lib().phnet_lane_targets_aug(*args, _ptr(flip2), _ptr(fwd), _stream()), "phnet_lane_targets_aug")
+            return out
+        clip, frag_count = _clip
+        if clip and p > LANE_TARGETS_MAX_POINTS_CLIP:
+            raise ValueError(f"lane_targets_clip: P = {p} outside 2 <= P <= 254 with clip")
+        if frag_count is not None:
+            _req(frag_count, torch.int32, "frag_count")
+            if tuple(frag_count.shape) != (f,) or frag_count.device != dev:
+                raise ValueError(f"lane_targets_clip: frag_count i32 [{f}] on {dev} expected")
+        check(lib().phnet_lane_targets_clip(*args, _ptr(flip2), _ptr(fwd), int(bool(clip)), _ptr(frag_count), _stream()),
+              "phnet_lane_targets_clip")
     return out
 
 
@@ -1154,6 +1166,15 @@ def lane_targets_aug(points, counts, lanes_num, offsets_ys, max_lanes: int, img_
     """lane_targets behind an augmented image: rule 0b of include/phnet_hip.h with flip2 i32 [F] and fwd f64 [F,6] (the source -> output
     matrices) on the device; either may be None (its step is skipped).  Keywords as lane_targets."""
     return lane_targets(points, counts, lanes_num, offsets_ys, max_lanes, img_h, img_w, strip_size, _aug=(flip2, fwd), **kw)
+
+
+def lane_targets_clip(points, counts, lanes_num, offsets_ys, max_lanes: int, img_h: float, img_w: float, strip_size: float, flip2=None,
+                      fwd=None, clip: bool = True, frag_count=None, **kw):
+    """lane_targets_aug with rule 0c of include/phnet_hip.h: clip = True cuts every lane at the image border and encodes each fragment
+    of more than 2 points as a lane of its own (P <= 254); clip = False is lane_targets_aug bit for bit.  frag_count i32 [F] on the
+    device, or None: written with the surviving fragments of each frame before the max_lanes cap.  Keywords as lane_targets."""
+    return lane_targets(points, counts, lanes_num, offsets_ys, max_lanes, img_h, img_w, strip_size, _aug=(flip2, fwd),
+                        _clip=(clip, frag_count), **kw)
 
 
 AUGMENT_TABLE_COLS, AUGMENT_MAX_SIDE = 16, 32768                  # the i32 table of phnet_augment_u8 (csrc/augment.hip)

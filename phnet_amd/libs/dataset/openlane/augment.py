@@ -11,9 +11,11 @@ numbered rules of include/phnet_hip.h.  The five neighbourhood ops (rule 7) live
 has one takes a staging pass (csrc/augment_stencil.hip, a second launch inside `phnet_augment_stencil_u8`) and the warp reads its taps
 from the staged image.  `AugmentSampler(..., neighbourhood=True)` draws them; the default does not, and keeps the earlier stream of draws.
 
-NOT built:
-  * clip_out_of_image_() on the line strings (targets.py): points outside the image are kept, and an affine moves more of them there;
-  * the reference's loop that retries a failing draw up to 30 times.
+Line clipping (clip_out_of_image_() on the line strings) is `TargetEncoder(..., clip=True)`, rule 0c of the target launch: an affine
+moves more points out of the image, so the augmented pipeline should run with it.  The reference's loop that retries a failing draw up
+to 30 times (transforms.py:63-75) is dead code for every input the rules accept - it retries only when transform_annotation raises, and
+with finite points it cannot (DESIGN.md "Training augmentation") - so nothing stands in its place but `frag_count=` of the encoder: one
+integer per frame, 0 where the draw left no lane.
 
 PARITY UNPINNED: imgaug, cv2 and skimage are not installed here and the reference ships no image fixture; cv2.warpAffine's tables,
 imgaug's colour-space round trips and cv2's fixed-point filters cannot be reproduced bit for bit.  The kernels are held exactly to a
