@@ -663,6 +663,44 @@ int phnet_tower_chain_fwd(const float* x, const float* const* params, int32_t T,
 int phnet_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay, const int64_t* step,
                      float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- guarded step: global-norm clip (torch.nn.utils.clip_grad_norm_, trainOL.py:221) and the non-finite skip of GradScaler.step
+ * (trainOL.py:225-227) for the flat arenas, decided on the device: phnet_grad_guard, then phnet_adamw_step_guarded.  No host
+ * synchronisation, no floating-point atomics, nothing to zero between steps; capturable.  The rules:
+ *  1. S = sum of g_i^2 over all n elements (padding included), each square and every addition in float64, in an order fixed by n and
+ *     PHNET_GUARD_CHUNK alone: element -> lane -> wavefront -> chunk partial -> ascending chunk index.  Chunk c holds elements
+ *     [c CHUNK, min(n, (c+1) CHUNK)); its 4-element vector q belongs to lane q % 256; a lane adds the squares of component e of its
+ *     vectors, in ascending q, into accumulator a_e, then takes (a0 + a1) + (a2 + a3); the 64 lanes of a wavefront (lanes 64w ..
+ *     64w+63) are added by an xor butterfly over the lane distances 32, 16, 8, 4, 2, 1; the chunk partial is ((w0 + w1) + w2) + w3;
+ *     S adds the chunk partials one by one in ascending c, starting from 0.  Two calls on the same buffer give the same bits,
+ *     whatever the grid, the CU count or the arrival order of workgroups.
+ *  2. nonfinite = the number of elements whose exponent field is all ones (an integer test on the bit pattern).
+ *  3. inv = 1 / grad_scale[0] in f32 when grad_scale != NULL, else 1.  norm = fl32(sqrt(S) * (double)inv): the norm of the unscaled,
+ *     unclipped gradient, what clip_grad_norm_ returns.
+ *  4. coef = min(1, max_norm / (norm + 1e-6f)) in f32 with PHNET_GUARD_CLIP (torch's clip_coef, clamped), else 1.  A NaN norm gives a
+ *     NaN coef, as in torch with error_if_nonfinite=False.
+ *  5. mult = fl32(coef * inv); the update sees g_eff_i = fl32(g_i * mult), one rounded f32 multiply.  g itself is never written
+ *     (torch's clip rewrites .grad in place; here .grad keeps the raw gradient).
+ *  6. skip = PHNET_GUARD_SKIP_NONFINITE && (nonfinite > 0 || (found_inf != NULL && found_inf[0] != 0) || !isfinite(norm)).
+ *  7. skip: p, m, v and step keep their bits; stats word 3 (skipped steps) += 1.
+ *  8. otherwise: step[0] += 1, then phnet_adamw_step's element update on g_eff (one shared device function).
+ * workspace: PHNET_GUARD_WS_BYTES_PER_CHUNK * ceil(n / PHNET_GUARD_CHUNK) bytes, 8-byte aligned (float64 partials, then uint32
+ * counts; written before it is read, never zeroed).  stats: PHNET_GUARD_STATS_WORDS int64 words - 0: {f32 norm, f32 mult},
+ * 1: this step was skipped (0 | 1), 2: nonfinite, 3: skipped steps in total (zero it once) - words 0-2 are written by every call.
+ * grad_scale / found_inf: what torch.amp.GradScaler hands an optimizer with _step_supports_amp_scaling (one f32 each), or NULL.
+ * n % 4 == 0; max_norm >= 0 (used only with PHNET_GUARD_CLIP; pass 0 without).
+ * phnet_adamw_step_guarded: phnet_adamw_step with `mult` (stats word 0, second float) and `skip` (stats word 1) read on the
+ * device; `step` is the counter phnet_grad_guard has already advanced. ---- */
+#define PHNET_GUARD_CHUNK 131072
+#define PHNET_GUARD_WS_BYTES_PER_CHUNK 12
+#define PHNET_GUARD_STATS_WORDS 4
+#define PHNET_GUARD_SKIP_NONFINITE 1
+#define PHNET_GUARD_CLIP 2
+int phnet_grad_guard(const float* g, int64_t n, void* workspace, uint64_t ws_bytes, int64_t* stats, int64_t* step,
+                     float max_norm, int32_t flags, const float* grad_scale, const float* found_inf, void* stream);
+int phnet_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay, const int64_t* step,
+                             float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                             const float* mult, const int64_t* skip, void* stream);
+
 /* residual + dropout + LayerNorm of the pre-norm decoder layers in one launch: t = res + dropout(x), h = LN_L(t)*w + b
  * (L <= 256), and its backward (dt = gradient arriving on the residual stream, may be NULL): dres, dx, dw, db. */
 int phnet_dropout_add_ln_fwd(const float* x, const float* res, const float* w, const float* b, float* t, float* h,

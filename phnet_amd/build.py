@@ -25,7 +25,7 @@ def _hipcc():
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = glob.glob(os.path.join(CSRC, "*.h"))
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(HERE), "include", "phnet_hip.h")]     # optim_guard.hip takes its constants from the public header
     newest_hdr = max([os.path.getmtime(h) for h in hdrs] + [0.0])
     objs, procs = [], []
     for s in srcs:

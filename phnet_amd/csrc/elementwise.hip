@@ -1,5 +1,6 @@
 // Small streaming kernels of the lane head (HBM-bound, 16-byte accesses where the shape allows).
 #include "common.h"
+#include "adamw_update.h"
 
 namespace {
 constexpr int NT = 256;
@@ -48,30 +49,14 @@ __global__ __launch_bounds__(NT) void gelu_dropout_bwd_kernel(const float* __res
 }
 
 // ---- AdamW over the flat parameter / gradient arenas (libs/utils/optimizer.py:33-35: optim.AdamW) -------------------------------
-// decoupled weight decay on elements [0, n_decay); same update order as torch's single-tensor AdamW:
-//   p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+// the element update itself is adamw_update4 (adamw_update.h), shared with the guarded step of optim_guard.hip
 __global__ __launch_bounds__(NT) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n4, long n_decay, const long long* __restrict__ step,
                                                    float lr, const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd)
 {
     const long i = (long)blockIdx.x * NT + threadIdx.x;
     if (i >= n4) return;
-    if (lr_dev) lr = lr_dev[0];                      // learning rate from device memory: a replayed hipGraph follows the schedule
-    const float t = (float)step[0];
-    const float c1 = 1.0f - powf(b1, t), c2s = sqrtf(1.0f - powf(b2, t));
-    const float step_size = lr / c1;
-    f32x4v pp = reinterpret_cast<f32x4v*>(p)[i], mm = reinterpret_cast<f32x4v*>(m)[i], vv = reinterpret_cast<f32x4v*>(v)[i];
-    const f32x4v gg = reinterpret_cast<const f32x4v*>(g)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float pe = pp[e];
-        if (i * 4 + e < n_decay) pe *= 1.0f - lr * wd;
-        const float me = b1 * mm[e] + (1.0f - b1) * gg[e];
-        const float ve = b2 * vv[e] + (1.0f - b2) * gg[e] * gg[e];
-        pe -= step_size * (me / (sqrtf(ve) / c2s + eps));
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-    }
-    reinterpret_cast<f32x4v*>(p)[i] = pp; reinterpret_cast<f32x4v*>(m)[i] = mm; reinterpret_cast<f32x4v*>(v)[i] = vv;
+    adamw_update4<false>(p, g, m, v, i, n_decay, step, lr, lr_dev, b1, b2, eps, wd, 1.0f);
 }
 
 // ---- cross-frame memory tokens (Router4OL.py:563-584): the positives' features in prior-index order, then the mean of

@@ -961,6 +961,52 @@ def adamw_step(p, g, m, v, n_decay: int, step, lr: float, beta1: float, beta2: f
                                  float(beta1), float(beta2), float(eps), float(weight_decay), _stream()), "phnet_adamw_step")
 
 
+GUARD_CHUNK = 131072             # PHNET_GUARD_CHUNK of include/phnet_hip.h: elements per chunk partial of the guard's reduction
+GUARD_WS_BYTES_PER_CHUNK = 12    # PHNET_GUARD_WS_BYTES_PER_CHUNK: one float64 partial and one uint32 count
+GUARD_STATS_WORDS = 4            # PHNET_GUARD_STATS_WORDS: {f32 norm, f32 mult} | last step skipped | non-finite count | skipped steps
+GUARD_SKIP_NONFINITE, GUARD_CLIP = 1, 2
+
+
+def grad_guard_workspace_bytes(n: int) -> int:
+    """Bytes of workspace phnet_grad_guard needs for an arena of n elements."""
+    return GUARD_WS_BYTES_PER_CHUNK * max(1, -(-int(n) // GUARD_CHUNK))
+
+
+def grad_guard(g, workspace, stats, step, max_norm: Optional[float], skip_nonfinite: bool, grad_scale=None, found_inf=None):
+    """Rules 1-7 of the guarded step (include/phnet_hip.h) over the flat gradient buffer g, on the device: writes
+    stats (int64[GUARD_STATS_WORDS]) and advances step (int64[1]) unless the step is to be skipped.  g is only read.
+    workspace: uint8 tensor of >= grad_guard_workspace_bytes(g.numel()); grad_scale / found_inf: float32 scalars on the
+    device as torch.amp.GradScaler hands them over, or None."""
+    _req(g, name="g"); _req(workspace, torch.uint8, "workspace"); _req(stats, torch.int64, "stats"); _req(step, torch.int64, "step")
+    if stats.numel() != GUARD_STATS_WORDS or step.numel() != 1:
+        raise ValueError("grad_guard: stats must have GUARD_STATS_WORDS elements and step one")
+    for t, name in ((grad_scale, "grad_scale"), (found_inf, "found_inf")):
+        if t is not None:
+            _req(t, name=name)
+            if t.numel() != 1:
+                raise ValueError(f"grad_guard: {name} must hold one element")
+    flags = (GUARD_SKIP_NONFINITE if skip_nonfinite else 0) | (GUARD_CLIP if max_norm is not None else 0)
+    check(lib().phnet_grad_guard(_ptr(g), g.numel(), _ptr(workspace), workspace.numel(), _ptr(stats), _ptr(step),
+                                 float(max_norm) if max_norm is not None else 0.0, flags, _ptr(grad_scale), _ptr(found_inf), _stream()),
+          "phnet_grad_guard")
+
+
+def adamw_step_guarded(p, g, m, v, n_decay: int, step, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                       mult, skip, lr_dev=None):
+    """adamw_step on fl32(g * mult[0]), or nothing at all when skip[0] != 0; mult (float32[1]) and skip (int64[1]) are read on the
+    device - the views of grad_guard's stats.  step has already been advanced by grad_guard."""
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (mult, "mult")):
+        _req(t, name=name)
+    _req(step, torch.int64, "step"); _req(skip, torch.int64, "skip")
+    if not (p.numel() == g.numel() == m.numel() == v.numel()):
+        raise ValueError("adamw_step_guarded: p/g/m/v lengths differ")
+    if lr_dev is not None:
+        _req(lr_dev, name="lr_dev")
+    check(lib().phnet_adamw_step_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), int(n_decay), _ptr(step), float(lr), _ptr(lr_dev),
+                                         float(beta1), float(beta2), float(eps), float(weight_decay), _ptr(mult), _ptr(skip), _stream()),
+          "phnet_adamw_step_guarded")
+
+
 def dropout_add(x, res=None, rng=None):
     """res + dropout(x) (either part optional) in one launch; dropout_add(dy, None, rng) is the backward of the dropout."""
     _req(x, name="x")

@@ -3,7 +3,7 @@
 torch.optim.AdamW semantics (reference: libs/utils/optimizer.py:33-35 builds optim.AdamW with weight decay on the
 matrices and none on biases / normalisation parameters, set_weight_decay ibid.).  Needs a GradArena built with
 flatten_params=True whose parameter list starts with the decayed parameters."""
-from typing import Iterable, Sequence, Tuple
+from typing import Iterable, Optional, Sequence, Tuple
 
 import torch
 
@@ -45,10 +45,19 @@ class FlatAdamW(torch.optim.Optimizer):
     around it: `CosineAnnealingLR(optimizer, ...)` stepped per iteration (trainOL.py:121-124,228) and
     `GradScaler.step(optimizer)` (trainOL.py:225-227).  The learning rate lives in DEVICE memory (`lr_dev`): `step()` pushes
     `param_groups[0]['lr']` there when it runs eagerly; a hipGraph-captured step reads whatever `sync_lr()` wrote before the
-    replay (GraphedTrainStep does that), so a schedule is followed without re-capturing."""
+    replay (GraphedTrainStep does that), so a schedule is followed without re-capturing.
+
+    max_grad_norm / skip_nonfinite (both off by default = the plain step): either one makes the optimizer GUARDED - `step()` first
+    reduces the gradient arena on the device (include/phnet_hip.h, "guarded step", rules 1-8) and the AdamW launch reads the
+    clip multiplier and the skip decision from device memory: global-norm clipping as `clip_grad_norm_(parameters, max_grad_norm)`
+    (trainOL.py:221) and the skip-on-inf/NaN of `GradScaler.step` (trainOL.py:225-227), capturable, without a host synchronisation.
+    The arena is never rewritten: `.grad` keeps the raw gradient, unlike torch's in-place clip.  A guarded instance takes
+    `grad_scale` / `found_inf` from torch.amp.GradScaler (`_step_supports_amp_scaling`).  What the guard saw is in `grad_norm`,
+    `clip_coef`, `last_skipped`, `nonfinite`, `skipped_steps` (device tensors, written by every guarded step) and
+    `guard_stats()`; none of it is part of `state_dict()`."""
 
     def __init__(self, arena: GradArena, n_decay: int, lr: float = 1e-3, betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, groups=None):
+                 weight_decay: float = 1e-2, groups=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         """groups: (decayed parameters, the rest), each in the order the CHECKPOINT numbers them (torch numbers parameters group by
         group in the order of the lists given to the optimizer; the reference passes named_parameters() order).  The arena may lay
         the same parameters out in any order as long as the decayed ones come first; default: the arena's order."""
@@ -62,6 +71,18 @@ class FlatAdamW(torch.optim.Optimizer):
         dev = arena.flat_params.device
         self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)     # on the device: graph-capturable
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"FlatAdamW: max_grad_norm must be >= 0, got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        if self.guarded:
+            self._guard_ws = torch.empty(K.grad_guard_workspace_bytes(arena.flat.numel()), dtype=torch.uint8, device=dev)
+            self._guard_stats = torch.zeros(K.GUARD_STATS_WORDS, dtype=torch.int64, device=dev)
+            f32 = self._guard_stats.view(torch.float32)
+            self.grad_norm, self.clip_coef = f32[0:1], f32[1:2]
+            self.last_skipped, self.nonfinite, self.skipped_steps = (self._guard_stats[i:i + 1] for i in (1, 2, 3))
+            self._step_supports_amp_scaling = True       # on the instance: an unguarded one keeps GradScaler's unscale-and-.item() path
         decayed, rest, seen = [], [], 0
         for p in arena.params:                                                  # arena order: decayed parameters first
             (decayed if seen < self.n_decay else rest).append(p)
@@ -135,10 +156,31 @@ class FlatAdamW(torch.optim.Optimizer):
         lr, betas, eps, wd = self._hyper()
         if not torch.cuda.is_current_stream_capturing():
             self.sync_lr()
+        if self.guarded:
+            return self._guarded_step(lr, betas, eps, wd)
         self.step_count.add_(1)
         weights_changed()                                       # raw-pointer update: invalidates folded eval weights (trunk._folded)
         K.adamw_step(self.arena.flat_params, self.arena.flat, self.exp_avg, self.exp_avg_sq, self.n_decay, self.step_count,
                      lr, betas[0], betas[1], eps, wd, lr_dev=self.lr_dev)
+
+    def _guarded_step(self, lr, betas, eps, wd):
+        """Guard launch (sum of squares + non-finite count of the arena, then norm / multiplier / skip decision and the counters:
+        `step_count` advances on the device unless the step is skipped), then the AdamW launch that reads both.  `grad_scale` /
+        `found_inf` are what GradScaler.step set on this instance for the call (device scalars), if it did."""
+        K.grad_guard(self.arena.flat, self._guard_ws, self._guard_stats, self.step_count, self.max_grad_norm, self.skip_nonfinite,
+                     grad_scale=getattr(self, "grad_scale", None), found_inf=getattr(self, "found_inf", None))
+        weights_changed()
+        K.adamw_step_guarded(self.arena.flat_params, self.arena.flat, self.exp_avg, self.exp_avg_sq, self.n_decay, self.step_count,
+                             lr, betas[0], betas[1], eps, wd, self.clip_coef, self.last_skipped, lr_dev=self.lr_dev)
+
+    def guard_stats(self) -> dict:
+        """What the last guarded step saw, with one device-to-host copy (a synchronisation: call it when you want to pay for it)."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdamW.guard_stats: built without max_grad_norm / skip_nonfinite")
+        words = self._guard_stats.cpu()
+        norm, mult = words[0:1].view(torch.float32).tolist()
+        return {"grad_norm": norm, "clip_coef": mult, "last_skipped": int(words[1]), "nonfinite": int(words[2]),
+                "skipped_steps": int(words[3])}
 
     def zero_grad(self, set_to_none: bool = False):
         """One memset of the gradient arena; the .grad views stay (set_to_none is ignored: the HIP kernels accumulate into them)."""
@@ -169,6 +211,8 @@ class FlatAdamW(torch.optim.Optimizer):
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        if self.guarded:
+            self.skipped_steps.zero_()                          # a monitoring total, not part of the checkpoint: restarts at 0
         if "state" not in sd:                                   # round-1 private layout (flat moments)
             self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"]); self.step_count.copy_(sd["step"])
             for g, saved in zip(self.param_groups, sd["param_groups"]):
