@@ -94,6 +94,46 @@ int phnet_lane_track(const float* kept_rows, const int64_t* num, int64_t B, int3
                      int32_t max_age, int32_t* trk_id, int32_t* trk_missed, int32_t* trk_hits, int32_t* trk_ext, float* trk_x,
                      int32_t* next_id, int32_t* track_id, int32_t* track_hits, void* stream);
 
+/* ---- lane overlay: the polylines of phnet_lane_points back on a picture (csrc/lane_draw.hip; replaces the host loops of the
+ * reference's test script, testOL.py:165-227 predlanesV2 / generate_seg_from_line - int() of every point, cv2.line(thickness = 12)
+ * lane by lane - and the 50/50 blend of libs/utils/utility.py:66-68).  One launch for F frames, no host synchronisation, no
+ * atomics; every element of every requested output is written exactly once on every call, so nothing has to be cleared.
+ * points f32 [F][L][S][2] (8-byte aligned), count i32 [F][L] (clamped to [0, S]), lanes_num i32 [F] (clamped to [0, L]) as
+ * phnet_lane_points writes them.  slot i32 [F][L] (phnet_lane_points) with track_id i32 [F][L] (phnet_lane_track): optional, colour
+ * by identity; slot alone is ignored.  Outputs, either or both: label_map u8 [F][out_h][out_w]; overlay u8 [F][out_h][out_w][3]
+ * packed RGB.  src (optional, read for the overlay only): F frames of out_h x out_w pixels, frame_stride bytes apart; src_format
+ * 0 = none, 1 = packed RGB rows of `pitch` >= 3 out_w bytes, 2 = NV12, 3 = YUYV - for 2 and 3 pitch, chroma_offset and csc_host [10]
+ * (HOST pointer) mean what they mean to phnet_preprocess_yuv with H0 = out_h, W0 = out_w.  palette u8 [256][3] on the device
+ * (needed with `overlay`); alpha 0..256.
+ *   1. point to pixel: px = trunc(double(x) * sx), py = trunc(double(y) * sy + oy) - float64, product and sum rounded separately,
+ *      truncation toward zero: Python's int() on the float64 expression (testOL.py:171).  sx = src_w, sy = src_h - crop, oy = crop
+ *      is the reference's mapping.  A point with x <= 0 or y <= 0 is skipped (testOL.py:169); so is a point that is NaN or +-inf or
+ *      whose px or py lies outside [-8192, 8192].  Consecutive surviving points of a lane form its segments; a lane with fewer than
+ *      2 survivors draws nothing.
+ *   2. coverage: pixel (u, v) belongs to a segment (x0, y0)-(x1, y1) iff, with q = (u - x0, v - y0), d = (x1 - x0, y1 - y0),
+ *      L2 = d.d, w = lane_width:  q.d <= 0: 4 q.q <= w^2;  q.d >= L2: 4 |(u - x1, v - y1)|^2 <= w^2;  else 4 (qx dy - qy dx)^2 <=
+ *      w^2 L2 - exact integers, the test of oracle/culane_cpu.py raster_lane and phnet_lane_raster, so a map agrees with what the
+ *      evaluator counts.  The pixel grid is the only clipping.  PARITY UNPINNED against cv2.line's scan conversion.
+ *   3. order: among the lanes covering a pixel the one with the highest packed index k wins (the painter's order of the
+ *      reference's loop, testOL.py:174-177).
+ *   4. value of lane k: without track_id v = k + 1.  With it id = track_id[f][slot[f][k]] (a slot outside [0, L) counts as id 0):
+ *      v = 1 + (id - 1) mod 254 for id >= 1, v = 255 for id <= 0 (a lane without an identity).  v = 0 is background.  The label map
+ *      stores v.
+ *   5. overlay: the source pixel as 8-bit RGB - NV12 / YUYV through the integer conversion of phnet_preprocess_yuv, chroma
+ *      replicated; without a source black.  v = 0: the source pixel.  Else out_c = (src_c (256 - alpha) + palette[v][c] alpha + 128)
+ *      >> 8: alpha = 256 is cv2.line onto the frame, alpha = 128 addWeighted(0.5, 0.5).
+ * A frame with lanes_num = 0 gives a zero map and an overlay equal to the converted source.
+ * PHNET_ERR_ARG before any launch: null points / count / lanes_num, points not 8-byte aligned, track_id without slot, no output,
+ * overlay without palette, F < 1 or F * ceil(out_w / 128) * ceil(out_h / 8) >= 2^31, L outside 1 <= L <= 64 or S outside
+ * 2 <= S <= 256, non-finite sx / sy / oy, out_h or out_w outside 1..4096, lane_width outside 1..256, alpha outside 0..256, an unknown
+ * src_format; with a source: null src, odd out_w (NV12, YUYV) or odd out_h (NV12), pitch or chroma_offset too small, frame_stride
+ * smaller than the bytes a frame spans, a frame that spans >= 2^31 bytes, a null or out-of-bound colour matrix (NV12, YUYV). */
+int phnet_lane_draw(const float* points, const int32_t* count, const int32_t* lanes_num, const int32_t* slot,
+                    const int32_t* track_id, int64_t F, int32_t L, int32_t S, double sx, double sy, double oy,
+                    int32_t out_h, int32_t out_w, int32_t lane_width, const uint8_t* src, int32_t src_format,
+                    int64_t frame_stride, int32_t pitch, int64_t chroma_offset, const int32_t* csc_host,
+                    const uint8_t* palette, int32_t alpha, uint8_t* label_map, uint8_t* overlay, void* stream);
+
 /* ---- training targets: annotated lane points -> the label rows the criterion consumes (csrc/lane_targets.hip; replaces the label
  * half of the reference's per-frame pipeline: datasetOL.py:47-59 crop / flip, transforms.py:251-347 transform_annotation,
  * filter_lane, sample_lane).  One launch for F frames, one wavefront per (frame, output row), no host synchronisation.

@@ -14,6 +14,7 @@
 // Camera formats (phnet_preprocess_yuv): NV12 and YUYV surfaces enter the same launch; every tap is converted to 8-bit RGB in
 // integers first (a 20-bit fixed-point matrix built by the host), so no RGB image is ever written to memory.
 #include "common.h"
+#include "csc.h"
 
 namespace {
 
@@ -79,17 +80,7 @@ __global__ __launch_bounds__(NT) void preprocess_kernel(
 }
 
 // ---- camera formats: the same launch with the colour conversion in front of the taps (no RGB image in memory) ----
-struct Csc { int bias[3]; int m[9]; };      // 20-bit fixed point, rows R, G, B; columns Y, U, V; bias = 2^19 - m0 y0 - 128 (m1 + m2)
-
-// c = clamp((m0 (Y - y0) + m1 (U - 128) + m2 (V - 128) + 2^19) >> 20, 0, 255) with the constant terms folded into `bias` by the entry:
-// the same integer (sums mod 2^32 of a value the entry checked to fit int32), three multiply-adds instead of three subtractions more.
-// 24-bit multiplies (full rate; the 32-bit one is quarter rate) are exact here: |m| < 2^23 is checked by the entry, Y, U, V < 2^8.
-__device__ __forceinline__ int csc_channel(const Csc& k, int c, int Y, int U, int V)
-{
-    const unsigned a = (unsigned)k.bias[c] + (unsigned)__mul24(k.m[3 * c], Y) + (unsigned)__mul24(k.m[3 * c + 1], U) + (unsigned)__mul24(k.m[3 * c + 2], V);
-    const int q = (int)a >> 20;                                    // arithmetic shift: floors
-    return q < 0 ? 0 : (q > 255 ? 255 : q);
-}
+// (Csc and csc_channel, the integer conversion of one source pixel: csc.h, shared with lane_draw.hip)
 
 // one thread per output pixel: each of its 4x4 taps is converted to 8-bit RGB first, chroma replicated (never interpolated).
 // YUYV = false: NV12, luma rows of `pitch` bytes at the frame's start, interleaved UV rows of `pitch` bytes from chroma_offset on,
@@ -207,19 +198,7 @@ PHNET_API int phnet_preprocess_yuv(const uint8_t* frames, float* out, uint8_t* o
     if (!frames || !out || !xi || !xc || !yi || !yc || !csc_host || !mean3_host || !std3_host) return PHNET_ERR_ARG;
     if (std3_host[0] == 0.f || std3_host[1] == 0.f || std3_host[2] == 0.f) return PHNET_ERR_ARG;
     Csc k;
-    const int y0 = csc_host[0];
-    if (y0 < 0 || y0 > 255) return PHNET_ERR_ARG;
-    for (int c = 0; c < 3; ++c) {
-        int64_t reach = 1 << 19;                                  // |accumulator| <= 255 * sum |m| + 2^19 must fit int32, a coefficient 24 bits
-        for (int j = 0; j < 3; ++j) {
-            k.m[3 * c + j] = csc_host[1 + 3 * c + j];
-            const int64_t a = k.m[3 * c + j];
-            reach += 255 * (a < 0 ? -a : a);
-            if (a <= -(1 << 23) || a >= (1 << 23)) return PHNET_ERR_ARG;
-        }
-        if (reach > INT32_MAX) return PHNET_ERR_ARG;
-        k.bias[c] = (int)((1u << 19) - (uint32_t)k.m[3 * c] * (uint32_t)y0 - 128u * ((uint32_t)k.m[3 * c + 1] + (uint32_t)k.m[3 * c + 2]));
-    }
+    if (!phnet_csc_from_host(csc_host, k)) return PHNET_ERR_ARG;
     const unsigned bpf32 = (unsigned)bpf, pitch32 = (unsigned)pitch, chroma32 = format == 0 ? (unsigned)chroma_offset : 0u;
     const dim3 grid((unsigned)(T * bpf));                          // bpf workgroups per frame: a workgroup never straddles two frames
     const float m0 = mean3_host[0], m1 = mean3_host[1], m2 = mean3_host[2], s0 = std3_host[0], s1 = std3_host[1], s2 = std3_host[2];

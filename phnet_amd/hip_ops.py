@@ -1150,6 +1150,70 @@ def lane_track(kept_rows, num, state, thr: float, max_age: int, out=None):
     return out
 
 
+LANE_DRAW_MAX_SIZE, LANE_DRAW_MAX_WIDTH, LANE_DRAW_COORD_BOUND = 4096, 256, 8192     # limits of phnet_lane_draw (csrc/lane_draw.hip)
+LANE_DRAW_FORMATS = {"none": 0, "rgb": 1, "nv12": 2, "yuyv": 3}
+
+
+def lane_draw(points, count, lanes_num, out_hw, sx: float, sy: float, oy: float, lane_width: int = 12, slot=None, track_id=None,
+              src=None, src_format: str = "none", pitch: int = 0, chroma_offset: int = 0, csc=None, palette=None, alpha: int = 256,
+              label_map=True, overlay=False):
+    """points f32 [F,L,S,2], count i32 [F,L], lanes_num i32 [F] (and slot i32 [F,L]) as lane_points returns them; track_id i32 [F,L]
+    as lane_track does -> dict(label_map u8 [F,H,W] or None, overlay u8 [F,H,W,3] or None) with (H, W) = out_hw: the lanes drawn by
+    the rules of include/phnet_hip.h (phnet_lane_draw), one launch, everything stays on the device (no sync).
+    label_map / overlay: True allocates, a tensor is written into, False / None leaves that output out.  src: u8 [F, ...] frames of
+    H x W pixels under the overlay (any shape; the frame stride is the bytes of src[0]), src_format "rgb" | "nv12" | "yuyv", with
+    pitch, chroma_offset and csc (10 ints, yuv_matrix) as ClipPreprocessor passes them to phnet_preprocess_yuv; palette u8 [256,3]."""
+    import ctypes
+    _req(points, name="points"); _req(count, torch.int32, "count"); _req(lanes_num, torch.int32, "lanes_num")
+    if points.dim() != 4 or points.shape[-1] != 2:
+        raise ValueError("lane_draw: points [F,L,S,2] expected")
+    f, l, s = points.shape[:3]
+    dev = points.device
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if tuple(count.shape) != (f, l) or tuple(lanes_num.shape) != (f,) or count.device != dev or lanes_num.device != dev:
+        raise ValueError(f"lane_draw: points {tuple(points.shape)} vs count {tuple(count.shape)} / lanes_num {tuple(lanes_num.shape)}")
+    for name, t in (("slot", slot), ("track_id", track_id)):
+        if t is not None:
+            _req(t, torch.int32, name)
+            if tuple(t.shape) != (f, l) or t.device != dev:
+                raise ValueError(f"lane_draw: {name} must be int32 {(f, l)} on {dev}, got {tuple(t.shape)}")
+    if track_id is not None and slot is None:
+        raise ValueError("lane_draw: track_id needs the slot of lane_points")
+    if src_format not in LANE_DRAW_FORMATS:
+        raise ValueError(f"lane_draw: src_format must be one of {sorted(LANE_DRAW_FORMATS)}, got {src_format!r}")
+    if (src is None) != (src_format == "none"):
+        raise ValueError("lane_draw: src and src_format go together")
+    stride = 0
+    if src is not None:
+        _req(src, torch.uint8, "src")
+        if src.dim() < 2 or src.shape[0] != f or src.device != dev:
+            raise ValueError(f"lane_draw: src must hold {f} frames on {dev}, got {tuple(src.shape)}")
+        stride = src[0].numel()
+        if src_format == "rgb" and not pitch:
+            pitch = 3 * w
+    outs = {}
+    for name, want, shape in (("label_map", label_map, (f, h, w)), ("overlay", overlay, (f, h, w, 3))):
+        if want is None or want is False:
+            outs[name] = None
+        elif want is True:
+            outs[name] = torch.empty(shape, dtype=torch.uint8, device=dev)
+        else:
+            _req(want, torch.uint8, name)
+            if tuple(want.shape) != shape or want.device != dev:
+                raise ValueError(f"lane_draw: {name} must be uint8 {shape} on {dev}, got {tuple(want.shape)}")
+            outs[name] = want
+    if palette is not None:
+        _req(palette, torch.uint8, "palette")
+        if tuple(palette.shape) != (256, 3) or palette.device != dev:
+            raise ValueError(f"lane_draw: palette must be uint8 [256,3] on {dev}")
+    csc_arr = None if csc is None else (ctypes.c_int32 * 10)(*[int(v) for v in csc])
+    check(lib().phnet_lane_draw(_ptr(points), _ptr(count), _ptr(lanes_num), _ptr(slot), _ptr(track_id), f, l, s, float(sx), float(sy),
+                                float(oy), h, w, int(lane_width), _ptr(src), LANE_DRAW_FORMATS[src_format], stride, int(pitch),
+                                int(chroma_offset), None if csc_arr is None else ctypes.cast(csc_arr, ctypes.c_void_p), _ptr(palette),
+                                int(alpha), _ptr(outs["label_map"]), _ptr(outs["overlay"]), _stream()), "phnet_lane_draw")
+    return outs
+
+
 LANE_TARGETS_MAX_IN_LANES, LANE_TARGETS_MAX_POINTS = 64, 256       # limits of phnet_lane_targets (csrc/lane_targets.hip)
 LANE_TARGETS_MAX_ROWS, LANE_TARGETS_MAX_OFFSETS = 64, 256
 LANE_TARGETS_MAX_POINTS_CLIP = 254                                # with rule 0c: a fragment has up to P + 2 points

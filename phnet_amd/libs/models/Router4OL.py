@@ -432,15 +432,16 @@ class DeviceResults:
         return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
 
     def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False,
-                    track: bool = False, max_tracks=None, max_age=None, match_thres=None):
+                    track: bool = False, max_tracks=None, max_age=None, match_thres=None, render=None):
         """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
         (phnet_amd.stream.LaneStream / LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.
         polylines=True: the step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast()).
-        track=True: the step also gives every kept row a stable id (stream.tracks; defaults: tracking.track_defaults)."""
+        track=True: the step also gives every kept row a stable id (stream.tracks; defaults: tracking.track_defaults).
+        render: a phnet_amd.overlay.LaneRenderer (with polylines=True) - the step also draws the lanes (stream.rendered)."""
         from phnet_amd import stream
         return getattr(stream, self.stream_class)(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every,
                                                   raw=raw, polylines=polylines, track=track, max_tracks=max_tracks, max_age=max_age,
-                                                  match_thres=match_thres)
+                                                  match_thres=match_thres, render=render)
 
     def track_clips(self, kept_rows: torch.Tensor, nums: torch.Tensor, max_tracks=None, max_age=None, match_thres=None):
         """Lane identities over the frames of a clip: kept_rows [T,max_lanes,6+S] / nums [T] of infer_device, or [B,T,..] / [B,T] of

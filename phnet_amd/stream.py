@@ -22,6 +22,9 @@ With `open_stream(..., track=True)` one launch after the decode (csrc/lane_track
 polylines) gives every kept row an id that stays with the lane from frame to frame; `s.tracks` holds `track_id` and `hits`
 (int32 [B,max_lanes], -1 / 0 where there is no lane) and `s.lanes_fast()` puts `track_id` into each polyline's metadata.
 
+With `open_stream(..., polylines=True, render=LaneRenderer(...))` the step's last launch (csrc/lane_draw.hip) draws the lanes: a
+label map and / or an overlay on the raw camera frame, in `s.rendered` (phnet_amd/overlay.py).
+
 `LaneStreamV2` is the same for the Router4OLV2 family (what `Router4OLV2.RouterOL.open_stream` returns): there the decoder runs
 for every stream and `stream_keys` (csrc/stream_v2.hip) picks each stream's key set - its memory window or its own tokens - from
 the device-side frame count.
@@ -105,13 +108,24 @@ class LaneStream:
     it is an evaluation protocol within one video, so ids carry across the chunk boundary.  Without track=True nothing is
     allocated, launched or returned differently.
 
-    With graph=True the returned tensors (and `polylines`, `tracks`) are the graph's static outputs: the next `step` overwrites them."""
+    render: a phnet_amd.overlay.LaneRenderer (needs polylines=True) - the last launch of the step (inside the captured graph, after
+    the polylines) is `hip_ops.lane_draw`; `rendered` = dict(label_map u8 [B,H,W] or None, overlay u8 [B,H,W,3] or None), allocated
+    once and rewritten by every step.  Lanes are coloured by `tracks` with track=True, else by their index; an overlay is drawn on
+    the raw camera frame when the stream has raw= (the renderer must take the same frames: LaneRenderer.for_preprocessor(raw)),
+    else on black.  What `step` returns does not change; without render= nothing is allocated, launched or returned differently.
+
+    With graph=True the returned tensors (and `polylines`, `tracks`, `rendered`) are the graph's static outputs: the next `step`
+    overwrites them."""
 
     def __init__(self, model, streams: int = 1, frame_hw: Tuple[int, int] = None, graph: bool = True, reset_every: Optional[int] = None,
                  raw=None, warmup: int = 2, polylines: bool = False, track: bool = False, max_tracks: Optional[int] = None,
-                 max_age: Optional[int] = None, match_thres: Optional[float] = None):
+                 max_age: Optional[int] = None, match_thres: Optional[float] = None, render=None):
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
+        if render is not None and not polylines:
+            raise ValueError("render= draws the polylines: open the stream with polylines=True")
+        if render is not None and render.overlay and raw is not None and tuple(render.frame_shape) != tuple(raw.frame_shape):
+            raise ValueError(f"render= draws on {render.src_format} frames {tuple(render.frame_shape)}, raw= takes {tuple(raw.frame_shape)}")
         det = model.head
         if frame_hw is None:
             frame_hw = (det.img_h, det.img_w)
@@ -133,6 +147,10 @@ class LaneStream:
             self.frames = torch.zeros((self.streams, *raw.frame_shape), dtype=torch.uint8, device=dev)
         else:
             self.frames = torch.zeros((self.streams, 3, *frame_hw), dtype=torch.float32, device=dev)
+        self.render, self.rendered, self._step_frames = render, None, None
+        if render is not None:
+            render.prepare(dev)                                   # the palette's copy must not fall into the capture
+            self.rendered = render.buffers((self.streams,), dev)
         self.frame_index = 0                                      # host-side count of steps, for reset_every only
         self.graph, self.out = None, None
         if graph:
@@ -154,6 +172,7 @@ class LaneStream:
         """infer_clips_device's loop body for T = 1 on the B streams, the memory taken from / pushed to the device ring."""
         model, det, st = self.model, self.model.head, self.state
         model._begin_clip()
+        self._step_frames = frames
         x = frames if self.raw is None else self.raw(frames)
         feats = model.backbone(x)
         front0 = det.stage0_front(feats[-1])
@@ -165,13 +184,16 @@ class LaneStream:
         return self._result(det, dec)
 
     def _result(self, det, dec):
-        """What `step` returns; first, with track=True, the ids of this frame's lanes and, with polylines=True, their points as
-        the last launch of the step."""
+        """What `step` returns; first, with track=True, the ids of this frame's lanes, with polylines=True their points and, with
+        render=, the picture of them as the last launch of the step."""
         if self.track_state is not None:
             K.lane_track(dec["kept_rows"].contiguous(), dec["num"].contiguous(), self.track_state, self.match_thr, self.max_age,
                          out=self.tracks)
         if self.want_polylines:
             self.polylines, self._rows = det.points_device(dec), dec["kept_rows"]      # the rows `slot` points into
+        if self.render is not None:                                                    # the step's last launch: the lanes on a picture
+            self.render.render(self.polylines, frames=self._step_frames if self.raw is not None else None, tracks=self.tracks,
+                               out=self.rendered)
         return dec["kept_rows"], dec["num"], dec["anchors"]
 
     def reset(self, mask=None):
@@ -236,6 +258,7 @@ class LaneStreamV2(LaneStream):
         """Router4OLV2.RouterOL.infer_clips_device's loop body for T = 1 on the B streams, keys and memory on the device."""
         model, det, st = self.model, self.model.head, self.state
         B, N = self.streams, det.num_priors
+        self._step_frames = frames
         x = frames if self.raw is None else self.raw(frames)
         feats = model.backbone(x)
         gate_rows = torch.empty((det.refine_layers, B * N), dtype=torch.float32, device=x.device)
