@@ -462,6 +462,35 @@ int phnet_lane_iou_groups(const uint32_t* masks, int32_t n_lanes, int32_t height
                           int32_t n_groups, int64_t n_entries, int32_t scale, double eps, double* iou, int64_t* area,
                           void* stream);
 
+/* ---- mask-level video metrics: the integer counts behind region similarity J and boundary F-measure F of a predicted and an
+ * annotated mask per frame (csrc/mask_metrics.hip; replaces the host work of evaluation/evaluate_vid.py:51-57 with
+ * video_metrics/jaccard.py and video_metrics/f_boundary.py: seg2bmap, two skimage binary_dilation(disk) calls and five np.sum per
+ * frame pair).  pred, gt u8 [n_frames][height][width], packed - for instance the label maps of phnet_lane_draw.  One memset node and
+ * two launches, no host synchronisation; integers only, so the counts do not depend on scheduling.
+ *   1. foreground: a pixel is foreground iff its byte is not 0; label values 1..255 all count (np.where(img > 0, 1, 0),
+ *      evaluate_vid.py:51-52).
+ *   2. boundary map b (seg2bmap, f_boundary.py:107-118, the path without resampling): with s = seg[y][x], e = seg[y][x+1],
+ *      so = seg[y+1][x], se = seg[y+1][x+1]:  y < H-1 and x < W-1: b = (s^e) | (s^so) | (s^se);  last row, x < W-1: b = s^e;  last
+ *      column, y < H-1: b = s^so;  the bottom-right pixel: b = 0.  A mask that is all foreground has an empty boundary map.
+ *   3. dilation: a pixel of dil(B) is set iff a set pixel of B lies at an offset (dx, dy) with dx^2 + dy^2 <= radius^2; nothing is
+ *      set outside the image.  skimage's disk(radius) under binary_dilation.  The half-width of the disk's row dy is the integer
+ *      square root of radius^2 - dy^2.  PARITY UNPINNED against skimage (not in the reference tree; the fixture pins scipy's
+ *      binary_dilation with the same footprint).
+ *   4. counts i64 [n_frames][7], in this order: area_pred, area_gt, area_both (foreground pixels of pred, gt, both), n_fg = |b_pred|,
+ *      n_gt = |b_gt|, fg_match = |b_pred & dil(b_gt)|, gt_match = |b_gt & dil(b_pred)|.  Every element is written on every call,
+ *      whatever `counts` and the workspace held.
+ *   5. limits: 1 <= height, width <= PHNET_MASK_METRICS_MAX_SIZE (the renderer's), 0 <= radius <= PHNET_MASK_METRICS_MAX_RADIUS
+ *      (0.008 x the diagonal of 4096 x 4096 is 47), n_frames >= 0; n_frames = 0 returns 0 and does nothing.  workspace: 8-byte aligned,
+ *      at least phnet_mask_metrics_workspace(...) = n_frames * 2 * height * ceil(width / 64) * 8 bytes (the two boundary maps as
+ *      64-pixel words; 0 for arguments outside the limits).  PHNET_ERR_ARG before any GPU call: a size, radius or n_frames outside the
+ *      limits, a null pred / gt / counts / workspace, a misaligned or too small workspace (its size is a function of the other
+ *      arguments, so it is one of them), n_frames * 2 * ceil(height / 32) * ceil(width / 512) >= 2^31. */
+#define PHNET_MASK_METRICS_MAX_RADIUS 127
+#define PHNET_MASK_METRICS_MAX_SIZE 4096
+uint64_t phnet_mask_metrics_workspace(int32_t n_frames, int32_t height, int32_t width, int32_t radius);
+int phnet_mask_metrics(const uint8_t* pred, const uint8_t* gt, int32_t n_frames, int32_t height, int32_t width, int32_t radius,
+                       void* workspace, uint64_t workspace_bytes, int64_t* counts, void* stream);
+
 /* ---- MaxPool2d(3,2,1): libs/models/resnet.py:217,297 ---- */
 int phnet_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* argmax, int32_t N, int32_t Hi, int32_t Wi, int32_t C, void* stream);
 int phnet_maxpool3x3s2_bwd(const float* dy, const uint8_t* argmax, float* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t C, void* stream);

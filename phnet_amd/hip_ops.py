@@ -1533,6 +1533,42 @@ def lane_iou_groups(masks, groups, width: int, scale: int = 1, eps: float = 0.0,
     return (iou, area) if want_area else iou
 
 
+MASK_METRICS_MAX_RADIUS, MASK_METRICS_MAX_SIZE = 127, 4096      # PHNET_MASK_METRICS_MAX_RADIUS / _MAX_SIZE of include/phnet_hip.h
+MASK_METRICS_COUNTS = ("area_pred", "area_gt", "area_both", "n_fg", "n_gt", "fg_match", "gt_match")
+
+
+def mask_metric_counts(pred, gt, radius: int, out=None):
+    """pred, gt u8 [.., H, W] (any leading dimensions, the same on both; a non-zero byte is foreground) -> int64 [.., 7]: the counts
+    of MASK_METRICS_COUNTS per frame by the rules of include/phnet_hip.h (phnet_mask_metrics; csrc/mask_metrics.hip) - the areas of
+    the two masks and of their intersection, the sizes of the two boundary maps, and how much of each boundary lies within `radius`
+    pixels of the other.  Three graph nodes, no sync; the boundary words live in the shared workspace.  `out`: an int64
+    [.., 7] tensor to write into (a captured graph keeps its address)."""
+    _req(pred, torch.uint8, "pred"); _req(gt, torch.uint8, "gt")
+    if pred.dim() < 2 or pred.shape != gt.shape or pred.device != gt.device:
+        raise ValueError(f"mask_metric_counts: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be u8 [.., H, W] of one shape on one device")
+    lead, (h, w) = tuple(pred.shape[:-2]), pred.shape[-2:]
+    radius = int(radius)
+    if not (1 <= h <= MASK_METRICS_MAX_SIZE and 1 <= w <= MASK_METRICS_MAX_SIZE):
+        raise ValueError(f"mask_metric_counts: height and width must be in 1..{MASK_METRICS_MAX_SIZE}, got {h} x {w}")
+    if not 0 <= radius <= MASK_METRICS_MAX_RADIUS:
+        raise ValueError(f"mask_metric_counts: radius must be in 0..{MASK_METRICS_MAX_RADIUS}, got {radius}")
+    n = 1
+    for d in lead:
+        n *= int(d)
+    if out is None:
+        out = torch.empty(lead + (7,), dtype=torch.int64, device=pred.device)
+    else:
+        _req(out, torch.int64, "out")
+        if tuple(out.shape) != lead + (7,) or out.device != pred.device:
+            raise ValueError(f"mask_metric_counts: out must be int64 {lead + (7,)} on {pred.device}, got {tuple(out.shape)}")
+    if n == 0:
+        return out
+    nbytes = lib().phnet_mask_metrics_workspace(n, h, w, radius)
+    ws = workspace(nbytes, pred.device)
+    check(lib().phnet_mask_metrics(_ptr(pred), _ptr(gt), n, h, w, radius, _ptr(ws), ws.numel(), _ptr(out), _stream()), "phnet_mask_metrics")
+    return out
+
+
 def tune_k_tile(code: int) -> None:
     """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on."""
     check(lib().phnet_tune_force_k_tile(code), "phnet_tune_force_k_tile")
