@@ -12,6 +12,15 @@ __global__ __launch_bounds__(THREADS) void conv_igemm_kernel(
     const float* __restrict__ addend, float* __restrict__ out, ConvShape g, int relu, float* __restrict__ stats)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    // The uniform-tap data gradient without buffer loads is the one that meets dilated dY images (stride-2 convolutions): those run
+    // igemm_tile's DIL form, every other problem the plain one - the instantiation linear_bwd_fused_kernel shares (linear_bwd.hip).
+    if constexpr (B_DGRAD && UNI && !BUF) {
+        if (g.in_dil == 2 && g.R <= 16 && g.S <= 16 && g.R * g.S <= 16) {
+            igemm_tile<BM, BN, B_DGRAD, BKT, UNI, false, MMA, PF, BUF, true>(X, W, bias, addend, out, g, relu, lds, blockIdx.x, gridDim.x,
+                                                                             blockIdx.z, nullptr, stats);
+            return;
+        }
+    }
     igemm_tile<BM, BN, B_DGRAD, BKT, UNI, false, MMA, PF, BUF>(X, W, bias, addend, out, g, relu, lds, blockIdx.x, gridDim.x, blockIdx.z,
                                                                nullptr, stats);
 }

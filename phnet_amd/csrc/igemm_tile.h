@@ -7,6 +7,20 @@ using namespace igemm;
 
 namespace {
 
+// Block -> tile for the class-ordered rows of a dilated data gradient (DIL below).  xcd_remap hands every XCD ONE run of
+// consecutive tiles, which here would be one parity class: the two XCDs that got the four-tap class of a 3x3 filter ran 32 K
+// tiles per workgroup while two others ran 8, and the launch took as long as those two.  So the tiles are cut into segments of
+// 8 * chunk and only inside a segment does an XCD (block & 7: workgroups go to the XCDs round robin) take a run of `chunk`
+// consecutive tiles - every XCD gets the same share of every class, neighbouring tiles still meet in one L2.  Bijective: the
+// full segments permute themselves, the remainder goes through xcd_remap.
+__device__ __forceinline__ unsigned xcd_remap_striped(unsigned bid, unsigned nblocks) {
+    const unsigned chunk = max(1u, min(16u, nblocks >> 6)), seg = 8u * chunk;
+    const unsigned full = nblocks / seg * seg;
+    if (bid >= full) return full + xcd_remap(bid - full, nblocks - full);
+    const unsigned s = bid / seg, w = bid - s * seg;
+    return s * seg + (w & 7u) * chunk + (w >> 3);
+}
+
 // The tile program is a device function so that one launch can run tiles of different GEMMs (linear_bwd_fused_kernel);
 // (block, nblocks, split) are what blockIdx.x / gridDim.x / blockIdx.z are for the plain kernel below.
 // AMASK: the A operand is a gradient that still has to pass a ReLU - element (row, k) counts only where amask (the saved
@@ -20,7 +34,18 @@ namespace {
 // out-of-range element is simply given an offset past the end of the tensor and the hardware returns zeros - no 64-bit
 // address arithmetic, no validity select when the tile is written to LDS (the loop is bound by its vector instruction
 // count: 90 per 6 MFMAs before, of which 44 are the split).
-template <int BM, int BN, bool B_DGRAD, int BKT, bool UNI, bool AMASK = false, int MMA = 0, int PF = 1, bool BUF = false>
+// DIL (needs B_DGRAD && UNI && !BUF; the caller guarantees g.in_dil == 2 and a filter of at most 16 taps, R, S <= 16:
+// conv_igemm_kernel branches to this instantiation at run time and keeps the plain one for every other problem): the data
+// gradient of a stride-2 convolution gathers from a dY image dilated by 2, so a dX pixel of parity class (y & 1, x & 1) can use
+// only the taps with r = (y + pad) mod 2, q = (x + pad) mod 2 - 1, 2, 2 or 4 of the 9 of a 3x3 / pad 1 filter, one class of four
+// for a 1x1 - and the other A rows used to be staged as zeros and multiplied.  Here the GEMM rows list the pixels class by class
+// (the class with the most live taps first; inside a class by (n, y >> 1, x >> 1)), so that a tile's rows share their live
+// taps, and the scalar tap walk visits only the taps of the classes the tile holds: its K extent is (live taps) x Ci, each
+// split walking the part of it that lies in its range of the full K; a tile without a live tap runs no K tile.  The per-row
+// parity test of the A loads stays, so a tile that holds several classes merely skips less.  Grid, tile count, split-K slabs
+// (indexed by the real pixel) and the reduce are untouched.
+template <int BM, int BN, bool B_DGRAD, int BKT, bool UNI, bool AMASK = false, int MMA = 0, int PF = 1, bool BUF = false,
+          bool DIL = false>
 __device__ __forceinline__ void igemm_tile(
     const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
     const float* __restrict__ addend, float* __restrict__ out, const ConvShape& g, int relu,
@@ -50,20 +75,69 @@ __device__ __forceinline__ void igemm_tile(
     const int M = g.N * g.Ho * g.Wo;
     const int K = g.R * g.S * g.Ci;
     const int tiles_n = (g.Co + BN - 1) / BN;
-    const unsigned tile = xcd_remap(block, nblocks);
+    const unsigned tile = DIL ? xcd_remap_striped(block, nblocks) : xcd_remap(block, nblocks);
     const int m0 = (int)(tile / tiles_n) * BM, n0 = (int)(tile % tiles_n) * BN;
-    const int k_begin = split * g.k_per_split;
-    const int k_end = min(K, k_begin + g.k_per_split);
+    int k_begin = split * g.k_per_split;
+    int k_end = min(K, k_begin + g.k_per_split);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * TM, wn = (wave & 1) * TN;
+
+    // ---- DIL: the pixel of each of the tile's rows (-1 past M), the tile's live taps, its share of their K tiles ----
+    unsigned long long tap_rs = 0, tap_qs = 0;             // the live taps in walking order, a nibble each
+    int tap_ord = 0;                                        // position of the walk in that list
+    int* row_pix = nullptr;
+    if constexpr (DIL) {
+        static_assert(B_DGRAD && UNI && !BUF && BM <= THREADS, "dilated data gradient: uniform tap, plain loads");
+        __shared__ int pix_s[BM];
+        row_pix = pix_s;
+        // order of the classes: c = 2 a + b holds the pixels with y & 1 == a ^ fy, x & 1 == b ^ fx; fy / fx put the parity
+        // with more live filter rows / columns first (an even coordinate starts at tap pad & 1, an odd one at the other)
+        const int e0 = g.pad & 1, o0 = e0 ^ 1;
+        const int fy = (g.R - o0 + 1) / 2 > (g.R - e0 + 1) / 2, fx = (g.S - o0 + 1) / 2 > (g.S - e0 + 1) / 2;
+        const int h0 = fy ? g.Ho >> 1 : (g.Ho + 1) >> 1, h1 = g.Ho - h0;         // image rows / columns of a = 0, 1 and b = 0, 1
+        const int w0 = fx ? g.Wo >> 1 : (g.Wo + 1) >> 1, w1 = g.Wo - w0;
+        const int cs1 = g.N * h0 * w0, cs2 = cs1 + g.N * h0 * w1, cs3 = cs2 + g.N * h1 * w0;      // first row of classes 1, 2, 3
+        const int m_hi = min(m0 + BM, M);
+        const unsigned held = (unsigned)(max(0, m0) < min(cs1, m_hi)) | (unsigned)(max(cs1, m0) < min(cs2, m_hi)) << 1 |
+                              (unsigned)(max(cs2, m0) < min(cs3, m_hi)) << 2 | (unsigned)(max(cs3, m0) < min(M, m_hi)) << 3;
+        // K as this tile walks it: (live taps) x Ci.  A split keeps the K tiles the host's cut of the FULL K gave it ([k_begin, k_end)
+        // so far) and walks the live ones among them - a run of the walk, since both orders are (r, q, c) - so every slab holds
+        // the partial sum it always held, bit for bit (the skipped products were exact zeros); a split whose range holds no live
+        // tile writes zeros.  (Dividing the live K tiles evenly instead regroups the sums of a 4-split launch: 6e-7 of the
+        // gradient, which 25 AdamW steps of bench.py turn into another loss.)
+        int live = 0, walk_begin = 0, walk_end = 0;     // tap (r, q) serves exactly one class
+        for (int r = 0; r < g.R; ++r)
+            for (int q = 0; q < g.S; ++q) {
+                const int c = 2 * (((r + g.pad) & 1) ^ fy) + (((q + g.pad) & 1) ^ fx);
+                if ((held >> c) & 1u) {
+                    tap_rs |= (unsigned long long)r << (4 * live);
+                    tap_qs |= (unsigned long long)q << (4 * live);
+                    ++live;
+                    const int k_tap = (r * g.S + q) * g.Ci;                  // where the tap starts in the full K
+                    walk_begin += min(max(k_begin - k_tap, 0), g.Ci);
+                    walk_end += min(max(k_end - k_tap, 0), g.Ci);
+                }
+            }
+        k_begin = walk_begin;
+        k_end = walk_end;
+        const int j = m0 + tid;
+        const int c = (j >= cs1) + (j >= cs2) + (j >= cs3);
+        const int l = j - (c == 0 ? 0 : c == 1 ? cs1 : c == 2 ? cs2 : cs3);
+        const int hc = (c >> 1) ? h1 : h0, wc = (c & 1) ? w1 : w0, hw = max(hc * wc, 1);
+        const int n = l / hw, rem = l - n * hw, yh = rem / max(wc, 1), xh = rem - yh * wc;
+        const int pixel = (n * g.Ho + 2 * yh + ((c >> 1) ^ fy)) * g.Wo + 2 * xh + ((c & 1) ^ fx);
+        if (tid < BM) pix_s[tid] = m0 + tid < M ? pixel : -1;
+        __syncthreads();
+    }
 
     // ---- per-thread gather coordinates of the A rows this thread stages (fixed over the K loop) ----
     RowCoord rc[A_LOADS];
     const int a_chunk = tid % CHUNKS, a_row = tid / CHUNKS;
 #pragma unroll
     for (int i = 0; i < A_LOADS; ++i) {
-        const int m = m0 + a_row + ROWS_PER_PASS * i;
+        int m = m0 + a_row + ROWS_PER_PASS * i;
         rc[i].ok = m < M;
+        if constexpr (DIL) m = row_pix[a_row + ROWS_PER_PASS * i];
         const int mm = rc[i].ok ? m : 0;
         const int n = mm / (g.Ho * g.Wo), rem = mm - n * (g.Ho * g.Wo);
         const int oy = rem / g.Wo, ox = rem - oy * g.Wo;
@@ -114,6 +188,11 @@ __device__ __forceinline__ void igemm_tile(
         uc0 = k_begin - rs * g.Ci;
         ur = rs / g.S;
         uq = rs - ur * g.S;
+        if constexpr (DIL) {                             // rs counts live taps here
+            tap_ord = min(rs, 15);
+            ur = (int)(tap_rs >> (4 * tap_ord)) & 15;
+            uq = (int)(tap_qs >> (4 * tap_ord)) & 15;
+        }
     }
 
     // The loads are BRANCH-FREE: an out-of-range element reads element 0 of its array and is zeroed when it is written to
@@ -224,6 +303,11 @@ __device__ __forceinline__ void igemm_tile(
             const int wq = uq == g.S;
             uq = wq ? 0 : uq;
             ur += wq;
+            if constexpr (DIL) {                         // the next live tap (past the last one: tap 0, the loads are masked by k_end)
+                tap_ord = min(tap_ord + wc, 15);
+                ur = (int)(tap_rs >> (4 * tap_ord)) & 15;
+                uq = (int)(tap_qs >> (4 * tap_ord)) & 15;
+            }
         }
     };
     auto store_lds = [&](int buf, const f32x4 (&a_reg)[A_LOADS], const f32x4 (&b_reg)[B_LOADS], const f32x4 (&a_relu)[AMASK ? A_LOADS : 1],
@@ -274,8 +358,9 @@ __device__ __forceinline__ void igemm_tile(
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm + i * 32 + frag_row(lane, e);
-                const bool ok = final_pass && addend && nok && m < M;
+                int m = m0 + wm + i * 32 + frag_row(lane, e);
+                if constexpr (DIL) m = row_pix[wm + i * 32 + frag_row(lane, e)];
+                const bool ok = final_pass && addend && nok && (DIL ? m >= 0 : m < M);
                 acc[i][j][e] = bv + (ok ? addend[(size_t)(ok ? m : 0) * g.Co + (ok ? n : 0)] : 0.f);
             }
     }
@@ -378,8 +463,9 @@ __device__ __forceinline__ void igemm_tile(
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm + i * 32 + frag_row(lane, e);
-                if (m < M) dst[(size_t)m * g.Co + n] = (final_pass && relu) ? fmaxf(acc[i][j][e], 0.f) : acc[i][j][e];
+                int m = m0 + wm + i * 32 + frag_row(lane, e);
+                if constexpr (DIL) m = row_pix[wm + i * 32 + frag_row(lane, e)];
+                if (DIL ? m >= 0 : m < M) dst[(size_t)m * g.Co + n] = (final_pass && relu) ? fmaxf(acc[i][j][e], 0.f) : acc[i][j][e];
             }
     }
 }
