@@ -29,24 +29,46 @@ __global__ __launch_bounds__(4 * NT) void lane_assign_tokens_kernel(
     float* __restrict__ tokens, unsigned char* __restrict__ valid)
 {
     extern __shared__ float cost[];                  // [N][MAXL], then [groups][E] column partial sums
+    __shared__ int sorted[MAXL];                     // the matched anchors as rows_sorted gets them, for the token rows below
     float* part = cost + N * MAXL;
-    // column sums of the features do not depend on the assignment: their loads are in flight while it runs
+    // Column sums of the features do not depend on the assignment.  Thread (grp, e) owns the rows n = grp, grp + groups, ... of
+    // column e: its last CB of them are requested here in one batch and stay in registers, unconsumed, until the assignment has
+    // returned (they arrive together with the assignment's own loads: one trip to memory); only a thread with more than CB rows
+    // (E = 256 and N > 128) sums the first ones before.  The sum runs in ascending n either way.
+    constexpr int CB = 32;
     const int e = threadIdx.x % E, grp = threadIdx.x / E, groups = (4 * NT) / E;
+    const int mine = (grp < groups && grp < N) ? (N - grp + groups - 1) / groups : 0;
+    const int head = mine > CB ? mine - CB : 0;
     float s = 0.f;
-    if (grp < groups)
-        for (int n = grp; n < N; n += groups) s += feat[(size_t)n * E + e];
-    lane_assign_block<false, 4>(pred, tgt, N, L, S, img_w, img_h, rows_by_col, rows_sorted, nullptr, nullptr, cost);
+    for (int i = 0; i < head; ++i) s += feat[(size_t)(grp + i * groups) * E + e];
+    float fb[CB];
+#pragma unroll
+    for (int u = 0; u < CB; ++u) fb[u] = feat[(size_t)(head + u < mine ? grp + (head + u) * groups : 0) * E + e];
+    lane_assign_block<false, 4, 18>(pred, tgt, N, L, S, img_w, img_h, rows_by_col, rows_sorted, nullptr, nullptr, cost, 0.25f, nullptr,
+                                    nullptr, nullptr, sorted);           // 18: the CB registers above leave no room for 72 columns
+#pragma unroll
+    for (int u = 0; u < CB; ++u) s = head + u < mine ? s + fb[u] : s;
     if (grp < groups) part[grp * E + e] = s;
-    __syncthreads();                                 // also orders rows_sorted (written by thread 0) before the reads below
+    __syncthreads();                                 // `sorted` (thread 0) was ordered by the barrier that ends lane_assign_block
     if (grp != 0) return;
+    // the token rows: all MAXL feature loads leave before the first is used (clamped row, the value selected by `ok`)
+    bool oks[MAXL];
+    float vs[MAXL];
+#pragma unroll
+    for (int l = 0; l < MAXL; ++l) {
+        const int r = l < L ? sorted[l] : -1;
+        oks[l] = r >= 0 && r < N;
+        vs[l] = feat[(size_t)(oks[l] ? r : 0) * E + e];
+    }
     float total = 0.f;
     for (int g2 = 0; g2 < groups; ++g2) total += part[g2 * E + e];
     float possum = 0.f;
     int cnt = 0;
-    for (int l = 0; l < L; ++l) {
-        const long long r = rows_sorted[l];
-        const bool ok = r >= 0 && r < N;
-        const float v = ok ? feat[(size_t)r * E + e] : 0.f;
+#pragma unroll
+    for (int l = 0; l < MAXL; ++l) {
+        if (l >= L) break;
+        const bool ok = oks[l];
+        const float v = ok ? vs[l] : 0.f;
         tokens[(size_t)l * E + e] = v;
         possum += v;
         cnt += ok;

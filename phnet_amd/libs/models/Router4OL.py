@@ -637,6 +637,8 @@ class RouterOL(nn.Module, DeviceResults):
                 matched, loss_b = self.criterion(out_b, lanes[b, t:t + 1], [gs[b] for gs in gate_clip])
                 total_loss = total_loss + loss_b
                 matched_all.append(matched)
+            if t == T - 1:
+                break                                                                        # the last frame's tokens have no reader
             with torch.no_grad():
                 tokens = []
                 for s_i, feat in enumerate(cur_cut):
@@ -739,11 +741,15 @@ class RouterOL(nn.Module, DeviceResults):
                 mem = (ring[t:t + W].view(-1, 1, E), ring_valid[t:t + W].view(-1)) if t > 0 else None
                 with torch.set_grad_enabled(not defer), PF.DropoutStream.items(BRANCH_B_SITES, stage * (T - 1) + t - 1 if t else 0, 0):
                     pred_b, line_b = det.forward_second(mem, tok_t[t].transpose(0, 1), stage, pri_t[t])
+                preds_b.append(pred_b)
+                lines_b.append(line_b.detach())
+                if t == T - 1:
+                    # slot W + t is read by the frames after t only (frame t' attends to ring[t' : t' + W], and so does
+                    # _branch_b_batch): the last frame's tokens have no reader, its slot stays zero / invalid as allocated
+                    continue
                 with torch.no_grad():                                            # assignment + the tokens it selects: one launch
                     K.lane_assign_tokens(pred_b[0].detach().contiguous(), lanes[t].contiguous(), det.img_w, det.img_h,
                                          tok_t[t].detach().contiguous(), (ring[W + t], ring_valid[W + t]))
-                preds_b.append(pred_b)
-                lines_b.append(line_b.detach())
             pa = front["pred_a"].split(1, dim=0)                                               # one cat in the backward
             gt = front["gate"].split(1, dim=0)
             for t in range(T):
