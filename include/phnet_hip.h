@@ -462,6 +462,74 @@ int phnet_lane_iou_groups(const uint32_t* masks, int32_t n_lanes, int32_t height
                           int32_t n_groups, int64_t n_entries, int32_t scale, double eps, double* iou, int64_t* area,
                           void* stream);
 
+/* ---- validation F1 on the device (csrc/lane_eval.hip; DESIGN.md "Validation F1"): the host arithmetic of the CULane-style
+ * evaluator around the two kernels above - the text files of evaluation/generate_lane.py:46-61, the chord-length spline of
+ * evaluation/culane/src/spline.cpp, the cv::line end points of lane_compare.cpp:22-49, the Kuhn-Munkres matching of
+ * include/hungarianGraph.hpp:39-67 and the counters of counter.cpp:83-161 - as two launches without a host synchronisation.  The
+ * pixel work between them is phnet_lane_raster and phnet_lane_iou_groups, unchanged.
+ *
+ * phnet_lane_eval_segments: one launch for F images, one workgroup per lane.  points f32 [F][L][S][2], count i32 [F][L],
+ * lanes_num i32 [F] as phnet_lane_points writes them; gt_points f32 [F][G][P][2], gt_count i32 [F][G], gt_num i32 [F]: the
+ * annotations in evaluator coordinates (what the evaluator reads from the annotation file).  Out, every element written on every
+ * call: segs i32 [F*(G+L)][C][5] with C = (max(S, P) - 1) * 50, rows (x0, y0, x1, y1, lane); lane_pts i32 [F][G+L].  Annotation g
+ * of image f is lane f*(G+L)+g, prediction k is lane f*(G+L)+G+k; a lane's rows start at lane*C and its unused rows carry lane -1,
+ * which phnet_lane_raster skips.  lane_pts is -1 for a lane that is not in the evaluator's list, else its number of points.
+ * All arithmetic in double, nothing contracted into an fma, unless a rule says otherwise:
+ *   1. presence.  Annotation g is present iff g < clamp(gt_num, 0, G), with clamp(gt_count, 0, P) points.  Prediction k is present
+ *      iff k < clamp(lanes_num, 0, L) and - in wire mode only - clamp(count, 0, S) > 2 (the len(pts) > 2 filter of the writer), with
+ *      clamp(count, 0, S) points.
+ *   2. mode 0, wire (the writer followed by the evaluator's reader): points are taken last to first, vx = (double(tx) * size_w) / 2,
+ *      vy = (double(ty) * size_h + crop_top) / 2, then each goes through the one-decimal text round trip: q = v * 10, k = rint(q); if
+ *      q is exactly a half-integer and the exact residual fma(v, 10, -q) is not zero, k is the neighbour on the side of the
+ *      residual; the value is float32(k / 10.0).  NaN and +-inf pass through.  mode 1, raw: the points are evaluator coordinates
+ *      in evaluator order already and are used as they are.
+ *   3. spline.  n >= 3 points: spline_interp_times(lane, 50) operation for operation - d[i] = p[i+1] - p[i], h[i] =
+ *      sqrt(dx*dx + dy*dy); A[i] = h[i], B[i] = 2*(h[i] + h[i+1]), C[i] = h[i+1], D[i] = 6*(d[i+1]/h[i+1] - d[i]/h[i]);  C[0] /= B[0],
+ *      D[0] /= B[0]; for i = 1..n-3: tmp = B[i] - A[i]*C[i-1], C[i] /= tmp, D[i] = (D[i] - A[i]*D[i-1]) / tmp;  M[n-2] = D[n-3], for
+ *      i = n-4..0: M[i+1] = D[i] - C[i]*M[i+2]; M[0] = M[n-1] = 0.  Interval i, k = 0..49: t = (h[i]/50)*k, b = d[i]/h[i] -
+ *      ((2*h[i])*M[i] + h[i]*M[i+1])/6, c = M[i]/2, dd = (M[i+1] - M[i])/(6*h[i]); the point is a + b*t + c*(t*t) + dd*((t*t)*t) with
+ *      a = p[i], cast to float32 (the product form is the rule: pow(t, 3) is not correctly rounded by contract); the last input
+ *      point is appended.  n == 2: the two points as they are.  n < 2: no segments.
+ *   4. end points: the float32 value as a double, NaN -> 0, rint (ties to even), clamp to +-8192; consecutive points form the rows.
+ * No table content causes an access outside the tables: every count read from memory is clamped before use.
+ * Limits (PHNET_ERR_ARG before any launch): 1 <= G, L <= PHNET_LANE_EVAL_MAX_LANES, 2 <= S, P <= PHNET_LANE_EVAL_MAX_POINTS, 1 <= F,
+ * F*(G+L)*C < 2^31, mode 0 or 1, size_h, size_w, crop_top finite, all pointers non-null.
+ *
+ * phnet_lane_eval_count: one launch, one workgroup walks the F images.  iou f64 [F][G][L] is phnet_lane_iou_groups (scale = 1,
+ * eps = 0) on the static table (f*(G+L), G, f*(G+L)+G, L, f*G*L); lane_pts as above; video i32 [F] (may be NULL = row 0): the
+ * accumulator row of each image, an image whose row is outside [0, V) is in no total.  Per image, count_im_pair on make_match
+ * exactly as written:
+ *   - the present annotations and predictions are compacted in order (n_anno rows, n_detect columns);
+ *   - sim[r][c] = 0 where either lane has fewer than 2 points, else the iou entry; a NaN stays a NaN;
+ *   - both sides empty: iou_im = 1; no annotation: fp = n_detect; no prediction: fn = n_anno;
+ *   - else Kuhn-Munkres on sim, transposed when n_anno > n_detect: row weights start at -1e5 and rise by `w < m ? m : w`, column
+ *     weights at 0; an edge is tight iff |lw + rw - m| < 1e-2; the search of a row visits columns in ascending order and re-enters
+ *     through the row a taken column is matched to; after a failed search dmin = 1e10 and then `d < dmin ? d : dmin` over the
+ *     (visited row, unvisited column) pairs; dmin == 1e10 ends the whole matching, else visited rows lose dmin, visited columns
+ *     gain it and the search repeats;
+ *   - a matched annotation adds its sim to the sum and is a true positive iff sim > threshold, else its match is withdrawn;
+ *     tp, fp = n_detect - tp, fn = n_anno - tp, iou_im = sum / n_detect.
+ * The relabelling passes of one image are capped at PHNET_LANE_EVAL_RELABEL_CAP: a failed search adds at least one column to the
+ * visited set of the next, so a row needs at most 16 passes and an image at most 16 * 16 = 256 on any matrix without infinities;
+ * the cap is four times that.  An image that reaches it counts as unmatched (tp = 0, fp = n_detect, fn = n_anno, iou_im = 0, no
+ * match) and adds 1 to overflow[0]: the kernel cannot spin.
+ * Out, per image, every element written on every call: tp, fp, fn i32 [F], iou_im f64 [F], anno_match i32 [F][G] (the caller's
+ * prediction index k of annotation g, -1 = none).  Totals, zeroed by the caller at reset and ADDED to: totals i64 [V][4] = (tp, fp,
+ * fn, images), iou_tot f64 [V], overflow i32 [1].  After a workgroup barrier one thread adds the images in ascending order, so the
+ * double sum has the host's order and does not depend on scheduling; no float atomics.
+ * Limits (PHNET_ERR_ARG before any launch): 1 <= G, L <= PHNET_LANE_EVAL_MAX_LANES, 1 <= F < 2^22, V >= 1, all pointers but `video`
+ * non-null. */
+#define PHNET_LANE_EVAL_MAX_LANES 16
+#define PHNET_LANE_EVAL_MAX_POINTS 256
+#define PHNET_LANE_EVAL_RELABEL_CAP 1024
+int phnet_lane_eval_segments(const float* points, const int32_t* count, const int32_t* lanes_num, const float* gt_points,
+                             const int32_t* gt_count, const int32_t* gt_num, int64_t F, int32_t G, int32_t L, int32_t S, int32_t P,
+                             int32_t mode, double size_h, double size_w, double crop_top, int32_t* segs, int32_t* lane_pts,
+                             void* stream);
+int phnet_lane_eval_count(const double* iou, const int32_t* lane_pts, int64_t F, int32_t G, int32_t L, double threshold,
+                          const int32_t* video, int32_t V, int32_t* tp, int32_t* fp, int32_t* fn, double* iou_im,
+                          int32_t* anno_match, int64_t* totals, double* iou_tot, int32_t* overflow, void* stream);
+
 /* ---- mask-level video metrics: the integer counts behind region similarity J and boundary F-measure F of a predicted and an
  * annotated mask per frame (csrc/mask_metrics.hip; replaces the host work of evaluation/evaluate_vid.py:51-57 with
  * video_metrics/jaccard.py and video_metrics/f_boundary.py: seg2bmap, two skimage binary_dilation(disk) calls and five np.sum per

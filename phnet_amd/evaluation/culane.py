@@ -13,6 +13,8 @@ batch of images are rasterised ONCE each into bit masks in HBM (`phnet_lane_rast
 pairwise intersections are bit counts (`phnet_lane_mask_stats`); spline, matching (the reference's Kuhn-Munkres with its 1e-2
 slack) and the counters are host arithmetic as in the reference.  No CPU fallback: without the HIP library this raises.
 The rasterisation rule (parity against OpenCV unpinned) is documented in include/phnet_hip.h and oracle/culane_cpu.py.
+`evaluate(..., device_pipeline=True)` and evaluation/online.py (LaneF1Meter: no files at all) run spline, matching and counters
+on the device as well (csrc/lane_eval.hip), with the same result.
 """
 import math
 import os
@@ -252,11 +254,15 @@ def count_im_pair(sim: Optional[np.ndarray], n_anno: int, n_detect: int, thresho
 
 # ---------------------------------------------------------------------------------------------- driver (evaluate.cpp:42-233)
 def evaluate(anno_dir: str, detect_dir: str, names: Sequence[str], width: int = 1920, height: int = 1080, lane_width: int = 10,
-             threshold: float = 0.4, output_file: Optional[str] = None, batch_images: int = 64, device="cuda") -> dict:
+             threshold: float = 0.4, output_file: Optional[str] = None, batch_images: int = 64, device="cuda",
+             device_pipeline: bool = False) -> dict:
     """`names`: the lines of the -l list file (image paths; the label files are `<dir><name without extension>.lines.txt`,
-    plain string concatenation as in evaluate.cpp:156-160).  Defaults are the binary's."""
+    plain string concatenation as in evaluate.cpp:156-160).  Defaults are the binary's.  device_pipeline: spline, matching and
+    counters run on the device too (evaluation/online.py, raw mode; at most 16 lanes of 256 points per file) - same result."""
     if lane_width < 1:
         raise ValueError("width_lane must be positive")              # evaluate.cpp:116-121
+    if device_pipeline:
+        return _evaluate_on_device(anno_dir, detect_dir, list(names), width, height, lane_width, threshold, output_file, batch_images, device)
     tp = fp = fn = 0
     iou = 0.0
     names = list(names)
@@ -270,6 +276,33 @@ def evaluate(anno_dir: str, detect_dir: str, names: Sequence[str], width: int = 
             _, a, b_, _, c, d = count_im_pair(sim, len(anno), len(det), threshold)
             tp += a; fp += b_; fn += c; iou += d
     return summarize(tp, fp, fn, iou, len(names), output_file)
+
+
+def _evaluate_on_device(anno_dir, detect_dir, names, width, height, lane_width, threshold, output_file, batch_images, device) -> dict:
+    """evaluate() through LaneF1Meter: the files are read as above, everything after them is device work, batch by batch."""
+    from . import online
+    images = []
+    for name in names:
+        stem = (name[:name.rfind(".")] if "." in name else name) + ".lines.txt"
+        images.append((read_lane_file(anno_dir + stem), read_lane_file(detect_dir + stem)))
+    if not images:
+        return summarize(0, 0, 0, 0.0, 0, output_file)
+    g = max(1, max(len(a) for a, _ in images))
+    l = max(1, max(len(d) for _, d in images))
+    p = max(2, max((len(x) for a, _ in images for x in a), default=2))
+    s = max(2, max((len(x) for _, d in images for x in d), default=2))
+    dev = torch.device(device)
+    meter = online.LaneF1Meter(height, width, lane_width, threshold, max_images=min(batch_images, len(images)), max_gt_lanes=g,
+                               max_gt_points=p, max_lanes=l, n_offsets=s, mode="raw", device=dev)
+    for b in range(0, len(images), batch_images):
+        batch = images[b:b + batch_images]
+        gt = [t.to(dev, non_blocking=True) for t in online.pack_eval_lanes([a for a, _ in batch], g, p)]
+        det = [t.to(dev, non_blocking=True) for t in online.pack_eval_lanes([d for _, d in batch], l, s)]
+        meter.update(dict(points=det[0], count=det[1], lanes_num=det[2]), *gt)
+    res = meter.compute()
+    if res["overflow"]:
+        raise RuntimeError(f"lane matching reached its iteration cap on {res['overflow']} images")
+    return summarize(res["tp"], res["fp"], res["fn"], meter.iou_sum(), len(names), output_file)
 
 
 def summarize(tp: int, fp: int, fn: int, iou: float, n_images: int, output_file: Optional[str] = None) -> dict:

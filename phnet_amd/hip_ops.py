@@ -1462,12 +1462,17 @@ def tower_chain_fwd(x, params, head_out, priors, ys, img_w, img_h):
 DEFAULT_MMA = "bf16x3"
 
 
-def lane_raster(segs, n_lanes: int, height: int, width: int, lane_width: int):
+def lane_raster(segs, n_lanes: int, height: int, width: int, lane_width: int, masks=None):
     """Bit masks [n_lanes][height][ceil(width/32)] (int32 words) of the thick poly-lines: segs [S][5] int32 = (x0, y0, x1, y1, lane)
-    (csrc/lane_iou.hip; the evaluator's cv::line canvases, evaluation/culane/src/lane_compare.cpp:17-49)."""
+    (csrc/lane_iou.hip; the evaluator's cv::line canvases, evaluation/culane/src/lane_compare.cpp:17-49).  masks: such a tensor,
+    zeroed by the caller, to OR the lines into (a captured graph keeps its address)."""
     _req(segs, torch.int32, "segs")
     assert segs.dim() == 2 and segs.shape[1] == 5
-    masks = torch.zeros((n_lanes, height, (width + 31) // 32), dtype=torch.int32, device=segs.device)
+    if masks is None:
+        masks = torch.zeros((n_lanes, height, (width + 31) // 32), dtype=torch.int32, device=segs.device)
+    else:
+        _req(masks, torch.int32, "masks")
+        assert tuple(masks.shape) == (n_lanes, height, (width + 31) // 32) and masks.device == segs.device
     check(lib().phnet_lane_raster(_ptr(segs), segs.shape[0], _ptr(masks), n_lanes, height, width, lane_width, _stream()), "phnet_lane_raster")
     return masks
 
@@ -1533,7 +1538,105 @@ def lane_iou_groups(masks, groups, width: int, scale: int = 1, eps: float = 0.0,
     return (iou, area) if want_area else iou
 
 
-MASK_METRICS_MAX_RADIUS, MASK_METRICS_MAX_SIZE = 127, 4096      # PHNET_MASK_METRICS_MAX_RADIUS / _MAX_SIZE of include/phnet_hip.h
+LANE_EVAL_MAX_LANES, LANE_EVAL_MAX_POINTS, LANE_EVAL_TIMES = 16, 256, 50     # limits of phnet_lane_eval_* (csrc/lane_eval.hip)
+LANE_EVAL_RELABEL_CAP = 1024                                                 # PHNET_LANE_EVAL_RELABEL_CAP of include/phnet_hip.h
+LANE_EVAL_MODES = {"wire": 0, "raw": 1}
+
+
+def lane_eval_rows(n_offsets: int, max_gt_points: int) -> int:
+    """C: the rows a lane owns in the segment table of `lane_eval_segments`."""
+    return (max(int(n_offsets), int(max_gt_points)) - 1) * LANE_EVAL_TIMES
+
+
+def _out_dict(name, out, shapes, dev):
+    if out is None:
+        return {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    for k, (shape, dt) in shapes.items():
+        _req(out[k], dt, k + " out")
+        if tuple(out[k].shape) != shape or out[k].device != dev:
+            raise ValueError(f"{name}: out[{k!r}] must be {shape} on {dev}, got {tuple(out[k].shape)} on {out[k].device}")
+    return {k: out[k] for k in shapes}
+
+
+def lane_eval_segments(points, count, lanes_num, gt_points, gt_count, gt_num, mode: str, size, crop_top: float, out=None):
+    """points f32 [F,L,S,2], count i32 [F,L], lanes_num i32 [F] as lane_points returns them and the annotations gt_points f32
+    [F,G,P,2], gt_count i32 [F,G], gt_num i32 [F] in evaluator coordinates -> dict(segs i32 [F*(G+L), C, 5], lane_pts i32 [F, G+L]):
+    the evaluator's cv::line table (spline, 50 segments per interval) by the rules of include/phnet_hip.h, one launch, no sync
+    (csrc/lane_eval.hip).  mode "wire": the predictions go through the .lines.txt round trip with size = (H_crop, W_org) and
+    crop_top; "raw": they are evaluator coordinates already.  Annotation g of image f is lane f*(G+L)+g, prediction k lane
+    f*(G+L)+G+k; unused rows carry lane -1.  out: such a dict to write into."""
+    _req(points, name="points"); _req(count, torch.int32, "count"); _req(lanes_num, torch.int32, "lanes_num")
+    _req(gt_points, name="gt_points"); _req(gt_count, torch.int32, "gt_count"); _req(gt_num, torch.int32, "gt_num")
+    if mode not in LANE_EVAL_MODES:
+        raise ValueError(f"lane_eval_segments: mode must be one of {sorted(LANE_EVAL_MODES)}, got {mode!r}")
+    if points.dim() != 4 or gt_points.dim() != 4 or points.shape[-1] != 2 or gt_points.shape[-1] != 2:
+        raise ValueError("lane_eval_segments: points [F,L,S,2] and gt_points [F,G,P,2] expected")
+    f, l, s = points.shape[:3]
+    g, p = gt_points.shape[1:3]
+    dev = points.device
+    if (gt_points.shape[0] != f or tuple(count.shape) != (f, l) or tuple(lanes_num.shape) != (f,) or tuple(gt_count.shape) != (f, g)
+            or tuple(gt_num.shape) != (f,) or any(t.device != dev for t in (count, lanes_num, gt_points, gt_count, gt_num))):
+        raise ValueError(f"lane_eval_segments: points {tuple(points.shape)} / count {tuple(count.shape)} / lanes_num "
+                         f"{tuple(lanes_num.shape)} / gt_points {tuple(gt_points.shape)} / gt_count {tuple(gt_count.shape)} / gt_num "
+                         f"{tuple(gt_num.shape)} do not belong together")
+    if not (1 <= g <= LANE_EVAL_MAX_LANES and 1 <= l <= LANE_EVAL_MAX_LANES and 2 <= s <= LANE_EVAL_MAX_POINTS
+            and 2 <= p <= LANE_EVAL_MAX_POINTS and f >= 1):
+        raise ValueError(f"lane_eval_segments: F = {f}, G = {g}, L = {l}, S = {s}, P = {p} outside 1 <= F, 1 <= G, L <= 16, 2 <= S, P <= 256")
+    c = lane_eval_rows(s, p)
+    if f * (g + l) * c >= 1 << 31:
+        raise ValueError("lane_eval_segments: F * (G + L) * C must stay below 2^31")
+    out = _out_dict("lane_eval_segments", out, dict(segs=((f * (g + l), c, 5), torch.int32), lane_pts=((f, g + l), torch.int32)), dev)
+    check(lib().phnet_lane_eval_segments(_ptr(points), _ptr(count), _ptr(lanes_num), _ptr(gt_points), _ptr(gt_count), _ptr(gt_num),
+                                         f, g, l, s, p, LANE_EVAL_MODES[mode], float(size[0]), float(size[1]), float(crop_top),
+                                         _ptr(out["segs"]), _ptr(out["lane_pts"]), _stream()), "phnet_lane_eval_segments")
+    return out
+
+
+def lane_eval_count(iou, lane_pts, n_gt: int, threshold: float, totals, iou_tot, overflow, video=None, out=None):
+    """iou f64 [F,G,L] (lane_iou_groups with scale = 1, eps = 0 on the table of one group per image) and lane_pts i32 [F,G+L] of
+    lane_eval_segments -> dict(tp, fp, fn i32 [F], iou_im f64 [F], anno_match i32 [F,G]): the evaluator's matching and counters
+    per image (count_im_pair / make_match as written; the rules are in include/phnet_hip.h), one launch, no sync.  The images are
+    ADDED, in ascending order, to totals i64 [V,4] = (tp, fp, fn, images) and iou_tot f64 [V] in the row video i32 [F] names (row
+    0 without it); overflow i32 [1] counts the images that reached the relabelling cap.  out: such a dict to write into."""
+    _req(iou, torch.float64, "iou"); _req(lane_pts, torch.int32, "lane_pts")
+    _req(totals, torch.int64, "totals"); _req(iou_tot, torch.float64, "iou_tot"); _req(overflow, torch.int32, "overflow")
+    if iou.dim() != 3 or lane_pts.dim() != 2:
+        raise ValueError("lane_eval_count: iou [F,G,L] and lane_pts [F,G+L] expected")
+    f, g, l = iou.shape
+    dev = iou.device
+    if g != int(n_gt) or tuple(lane_pts.shape) != (f, g + l) or lane_pts.device != dev:
+        raise ValueError(f"lane_eval_count: iou {tuple(iou.shape)} vs lane_pts {tuple(lane_pts.shape)} with G = {n_gt}")
+    if not (1 <= g <= LANE_EVAL_MAX_LANES and 1 <= l <= LANE_EVAL_MAX_LANES and 1 <= f < 1 << 22):
+        raise ValueError(f"lane_eval_count: F = {f}, G = {g}, L = {l} outside 1 <= F < 2^22, 1 <= G, L <= 16")
+    v = totals.shape[0]
+    if totals.dim() != 2 or totals.shape[1] != 4 or v < 1 or tuple(iou_tot.shape) != (v,) or overflow.numel() != 1 or \
+            any(t.device != dev for t in (totals, iou_tot, overflow)):
+        raise ValueError(f"lane_eval_count: totals i64 [V,4], iou_tot f64 [V] and overflow i32 [1] on {dev} expected")
+    if video is not None:
+        _req(video, torch.int32, "video")
+        if tuple(video.shape) != (f,) or video.device != dev:
+            raise ValueError(f"lane_eval_count: video must be int32 [{f}] on {dev}")
+    out = _out_dict("lane_eval_count", out, dict(tp=((f,), torch.int32), fp=((f,), torch.int32), fn=((f,), torch.int32),
+                                                 iou_im=((f,), torch.float64), anno_match=((f, g), torch.int32)), dev)
+    check(lib().phnet_lane_eval_count(_ptr(iou), _ptr(lane_pts), f, g, l, float(threshold), _ptr(video), v, _ptr(out["tp"]),
+                                      _ptr(out["fp"]), _ptr(out["fn"]), _ptr(out["iou_im"]), _ptr(out["anno_match"]), _ptr(totals),
+                                      _ptr(iou_tot), _ptr(overflow), _stream()), "phnet_lane_eval_count")
+    return out
+
+
+def lane_iou_groups_device(masks, dev_groups, n_entries: int, width: int, out):
+    """lane_iou_groups for a caller that keeps its (host-checked, see check_iou_groups) table on the device and owns the output:
+    dev_groups i32 [n_groups, 5], out f64 with n_entries elements; scale = 1, eps = 0.  Nothing is allocated or copied."""
+    _req(masks, torch.int32, "masks"); _req(dev_groups, torch.int32, "groups"); _req(out, torch.float64, "out")
+    n_lanes, height = int(masks.shape[0]), masks.shape[1]
+    assert masks.dim() == 3 and masks.shape[2] == (width + 31) // 32 and dev_groups.dim() == 2 and dev_groups.shape[1] == 5
+    assert out.numel() == n_entries and out.device == masks.device and dev_groups.device == masks.device
+    check(lib().phnet_lane_iou_groups(_ptr(masks), n_lanes, height, width, _ptr(dev_groups), dev_groups.shape[0], int(n_entries), 1, 0.0,
+                                      _ptr(out), None, _stream()), "phnet_lane_iou_groups")
+    return out
+
+
+MASK_METRICS_MAX_RADIUS, MASK_METRICS_MAX_SIZE = 127, 4096     # PHNET_MASK_METRICS_MAX_RADIUS / _MAX_SIZE of include/phnet_hip.h
 MASK_METRICS_COUNTS = ("area_pred", "area_gt", "area_both", "n_fg", "n_gt", "fg_match", "gt_match")
 
 
