@@ -775,6 +775,25 @@ int phnet_rowchain_fwd(const float* in, const float* resid, const float* Wa, con
                        int32_t R, int32_t E, int32_t FF, int32_t NG, float eps,
                        const uint64_t* rng_state, uint64_t call_a, uint64_t call_f, uint64_t call_3, float drop_p, void* stream);
 
+/* ---- [chain A] -> cross-attention core -> [chain B] of a pre-norm decoder layer in one launch, forward only: the bits of
+ * phnet_rowchain_fwd -> phnet_attention_fwd -> phnet_rowchain_fwd.  B items as contiguous row blocks: item b owns rows
+ * [b*Lq, (b+1)*Lq) of in / resid / the outputs and keys [b*Lk, (b+1)*Lk) of k / v (row strides sk / sv, heads packed along the row) /
+ * key_valid u8[B*Lk] (optional).  Chain A (Wa0 != NULL): in = the self-attention output, resid its residual,
+ * t = resid + dropout(in @ Wa0^T + ba0) [site call_a0], q = LayerNorm(t; ln0w, ln0b, eps0) @ Wq^T + bq; without it in = q and
+ * resid = t of an earlier launch.  Attention weights: dropout site call_c, probability attn_drop_p.  Chain B: out-projection
+ * Wa / ba [site call_a], LayerNorm ln1, feed-forward W1 / b1 / W2 / b2 [sites call_f, call_3], LayerNorm ln2, optional next
+ * projection Wg / bg [NG][E]; outputs as in phnet_rowchain_fwd.  Supported: E = 128 = 16 H, FF = 256, 1 <= Lk <= 64; anything
+ * else returns PHNET_ERR_ARG and launches nothing (the caller keeps the three launches). ---- */
+int phnet_rowchain_attn_fwd(const float* in, const float* resid, const float* Wa0, const float* ba0, const float* ln0w,
+                            const float* ln0b, const float* Wq, const float* bq, float eps0,
+                            const float* k, const float* v, int64_t sk, int64_t sv, const uint8_t* key_valid,
+                            const float* Wa, const float* ba, const float* ln1w, const float* ln1b,
+                            const float* W1, const float* b1, const float* W2, const float* b2, const float* ln2w, const float* ln2b,
+                            const float* Wg, const float* bg, float* t_out, float* h_out, float* y_out,
+                            int32_t B, int32_t Lq, int32_t Lk, int32_t H, int32_t E, int32_t FF, int32_t NG, float eps,
+                            const uint64_t* rng_state, uint64_t call_a0, uint64_t call_c, uint64_t call_a, uint64_t call_f,
+                            uint64_t call_3, float drop_p, float attn_drop_p, void* stream);
+
 /* ---- tower weights of a lane-head branch (libs/models/Router4OL.py:68-99, 308-326: T towers of two Linear + ReLU layers and one
  * Linear head each) assembled for the 3-GEMM chain, and their gradients scattered back: one launch each instead of the ~12
  * torch.cat / block_diag launches per branch and clip and the ~40 of their autograd backward.  params / grads: HOST arrays of 6*T

@@ -10,19 +10,19 @@
 // Tensors are addressed with row strides, so q/k/v may be column slices of a packed [L,3E] projection output and the
 // gradients are written straight into the packed gradient buffer.
 #include "common.h"
+#include "attn_device.h"
 
 namespace {
 
-constexpr int D = 16;                 // head width
+using namespace attn_dev;       // D, LPR, f4, dot16, quad_sum / quad_max and the forward body of one (query row, head)
+
 constexpr int NT = 256;
-constexpr int LPR = 16;               // lanes per row: each walks every 16th key (or query) - the per-lane loop is the critical path
 constexpr int ROWS = NT / LPR;        // 16 rows (queries or keys) per workgroup -> 8 heads x 15 tiles = 120+ workgroups per launch
 constexpr int MAXK = 256;             // keys per head held in LDS
 
 struct AttnShape { int Lq, Lk, H; long sq, sk, sv, so; float scale, keep_scale; };      // gridDim.z = batch: clip b owns rows [b*Lq, (b+1)*Lq) / [b*Lk, (b+1)*Lk)
 
 constexpr int DP = D + 4;              // LDS row pitch: 16-byte aligned rows (b128 access), 4 consecutive rows on distinct banks
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // Stage head h of `rows` rows (<= MAXK) of two row-strided arrays into LDS.  All global loads are issued before the first
 // LDS store (branch-free, clamped addresses): one memory latency for the whole tile instead of one per loop trip.
@@ -48,26 +48,6 @@ __device__ __forceinline__ void stage_pair(const float* __restrict__ a, long sa,
     }
 }
 
-// 16-wide dot products with four independent partial sums (a single chain of 16 dependent FMAs is pure latency here)
-__device__ __forceinline__ float dot16(const float (&a)[D], const float* b) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d += 4) { s0 += a[d] * b[d]; s1 += a[d + 1] * b[d + 1]; s2 += a[d + 2] * b[d + 2]; s3 += a[d + 3] * b[d + 3]; }
-    return (s0 + s1) + (s2 + s3);
-}
-
-// LPR adjacent lanes -> one row: reduce across them
-__device__ __forceinline__ float quad_sum(float v) {
-#pragma unroll
-    for (int o = 1; o < LPR; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float quad_max(float v) {
-#pragma unroll
-    for (int o = 1; o < LPR; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                       const unsigned char* __restrict__ key_valid, const unsigned char* __restrict__ keep,
                                                       float* __restrict__ o, float* __restrict__ lse, AttnShape g, DropRng rng)
@@ -84,45 +64,18 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const float* __restrict__ 
     // the query row first (branch-free float4 loads): its latency overlaps the K/V staging instead of following the barrier
     const bool live = row < g.Lq;
     float qr[D];
-    {
-        const f4* qp = reinterpret_cast<const f4*>(q + (size_t)(live ? row : 0) * g.sq + h * D);
-#pragma unroll
-        for (int c = 0; c < D / 4; ++c) {
-            const f4 t = qp[c];
-            qr[4 * c] = t.x * g.scale; qr[4 * c + 1] = t.y * g.scale; qr[4 * c + 2] = t.z * g.scale; qr[4 * c + 3] = t.w * g.scale;
-        }
-    }
+    load_q_scaled(qr, q + (size_t)(live ? row : 0) * g.sq + h * D, g.scale);
     stage_pair(k, g.sk, v, g.sv, h, g.Lk, Ks, Vs, 1.0f);
     for (int i = threadIdx.x; i < g.Lk; i += NT) valid[i] = key_valid ? key_valid[i] : 1;
     __syncthreads();
-    float m = -INFINITY, l = 0.f, acc[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) acc[d] = 0.f;
     const unsigned char* kp = keep ? keep + ((size_t)h * g.Lq + (live ? row : 0)) * g.Lk : nullptr;
     const uint64_t seed = phnet_rng_seed(rng), rbase = ((uint64_t)h * g.Lq + (live ? row : 0)) * g.Lk;      // within batch entry blockIdx.z
-    for (int kk = part; kk < g.Lk; kk += LPR) {
-        if (!valid[kk]) continue;
-        const float s = dot16(qr, Ks[kk]);
-        const float mn = fmaxf(m, s);
-        const float c = expf(m - mn), e = expf(s - mn);
-        l = l * c + e;
-        const bool kept = kp ? kp[kk] != 0 : (!rng.thresh || phnet_rng_keep(seed, phnet_rng_index_b(rng, blockIdx.z, rbase + kk), rng.thresh));
-        const float ed = kept ? e * g.keep_scale : 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) acc[d] = acc[d] * c + ed * Vs[kk][d];
-        m = mn;
-    }
-    // merge the LPR partial (m, l, acc) of the row
-    const float mt = quad_max(m);
-    const float c = (m == -INFINITY) ? 0.f : expf(m - mt);
-    l = quad_sum(l * c);
-#pragma unroll
-    for (int d = 0; d < D; ++d) acc[d] = quad_sum(acc[d] * c);
+    float out[D];
+    const float ls = attn_row_head<DP, true>(qr, &Ks[0][0], &Vs[0][0], valid, g.Lk, part, kp, rng, seed, blockIdx.z, rbase, g.keep_scale, out);
     if (live && part == 0) {
-        const float inv = l > 0.f ? 1.0f / l : 0.f;
 #pragma unroll
-        for (int d = 0; d < D; ++d) o[(size_t)row * g.so + h * D + d] = acc[d] * inv;
-        lse[(size_t)h * g.Lq + row] = mt + logf(l);
+        for (int d = 0; d < D; ++d) o[(size_t)row * g.so + h * D + d] = out[d];
+        lse[(size_t)h * g.Lq + row] = ls;
     }
 }
 

@@ -21,6 +21,7 @@
 // 16 k's and reads the matching float4 of its activation row from LDS - the k order inside a 16-group is permuted identically for
 // both operands, which a dot product does not see.
 #include "common.h"
+#include "attn_device.h"
 
 namespace {
 
@@ -225,6 +226,161 @@ __global__ __launch_bounds__(NT) void rowchain_kernel(RowChain p)
         }, first_of<PRE, E / 16>(pg));
 }
 
+// ---- a row chain with the cross-attention core as a stage (forward only) ---------------------------------------------------------
+// The three launches [out-projection + residual + LayerNorm + q] -> cross-attention core -> [out-projection + residual + LayerNorm +
+// feed-forward + residual + LayerNorm (+ next projection)] as ONE: cross-attention is row-local in the queries - a workgroup that
+// owns 16 query rows needs only the memory's K/V (<= LKMAX keys, all heads, staged in LDS beside the row buffers).
+//   chain A (optional) = the first launch, t and q stay in LDS; absent: t and q are read from global memory;
+//   cross-attention    = the shared body of attn_fwd_kernel (attn_device.h) for the 16 rows x H heads, 32 (row, head) per sweep;
+//   chain B            = the third launch with the attention result as `in` and t as the residual.
+// Every stage repeats the statements of rowchain_kernel / attn_fwd_kernel with the same dropout sites and element indices, so
+// the outputs are the bits of the three launches.  Batch: item b = blockIdx.y owns rows [b*Lq, (b+1)*Lq) and keys [b*Lk, (b+1)*Lk).
+constexpr int LKMAX = 64;                          // keys held in LDS (the model's memory: <= 40)
+
+struct RowChainAttn {
+    const float *in, *resid;                       // chain A: [R][E] attention output and residual;  no chain A: q and t, [R][E]
+    const float *Wa0, *ba0, *ln0w, *ln0b, *Wq, *bq;  // chain A: out-projection, LayerNorm, q projection [E][E]; Wa0 null = no chain A
+    const float *k, *v;                            // [B*Lk][.] row strides sk / sv, heads packed along the row
+    const unsigned char* key_valid;                // u8[B*Lk] or null
+    RowChain c;                                    // chain B (in / resid unused; R = B*Lq)
+    long sk, sv;
+    int Lq, Lk;
+    float eps0, qscale, keep_scale;
+    DropRng rng0, rngC;                            // dropout of chain A's residual, of the attention weights
+};
+
+template <int E, int FF>
+__global__ __launch_bounds__(NT) void rowchain_attn_kernel(RowChainAttn g)
+{
+    constexpr int EP = E + 4, FP = FF + 4, H = E / attn_dev::D;
+    static_assert(ROWS * H % (NT / attn_dev::LPR) == 0, "whole sweeps of (row, head) pairs");
+    extern __shared__ __attribute__((aligned(16))) float rc_lds[];
+    __shared__ unsigned char valid[LKMAX];
+    float* xs = rc_lds;                      // [ROWS][EP] stage input, later the normalised rows h
+    float* ts = xs + ROWS * EP;              // [ROWS][EP] residual stream t
+    float* fs = ts + ROWS * EP;              // [ROWS][FP] q of the cross-attention (pitch EP), later the feed-forward hidden
+    float* Ks = fs + ROWS * FP;              // [Lk][EP] keys, all heads
+    float* Vs = Ks + g.Lk * EP;              // [Lk][EP] values
+    const RowChain& p = g.c;
+    const int Lk = g.Lk;
+    const long row0 = (long)blockIdx.y * g.Lq + (long)blockIdx.x * ROWS;
+    const long R = (long)(blockIdx.y + 1) * g.Lq;             // the item's last row + 1: a tile never straddles two items
+    // ---- K / V of the item (all heads) and the key-valid bytes ----
+    {
+        const float* kb = g.k + (size_t)blockIdx.y * Lk * g.sk;
+        const float* vb = g.v + (size_t)blockIdx.y * Lk * g.sv;
+        for (int i = threadIdx.x; i < Lk * (E / 4); i += NT) {
+            const int r = i / (E / 4), c4 = (i - r * (E / 4)) * 4;
+            *reinterpret_cast<f4*>(Ks + r * EP + c4) = *reinterpret_cast<const f4*>(kb + (size_t)r * g.sk + c4);
+            *reinterpret_cast<f4*>(Vs + r * EP + c4) = *reinterpret_cast<const f4*>(vb + (size_t)r * g.sv + c4);
+        }
+        for (int i = threadIdx.x; i < Lk; i += NT) valid[i] = g.key_valid ? g.key_valid[(size_t)blockIdx.y * Lk + i] : 1;
+    }
+    if (g.Wa0) {
+        // ---- chain A: t = resid + dropout(in @ Wa0^T + ba0); h = LayerNorm(t); q = h @ Wq^T + bq ----
+        for (int i = threadIdx.x; i < ROWS * (E / 4); i += NT) {
+            const int r = i / (E / 4), c4 = (i - r * (E / 4)) * 4;
+            f4 v = {0.f, 0.f, 0.f, 0.f};
+            if (row0 + r < R) v = *reinterpret_cast<const f4*>(g.in + (size_t)(row0 + r) * E + c4);
+            *reinterpret_cast<f4*>(xs + r * EP + c4) = v;
+        }
+        __syncthreads();
+        {
+            const uint64_t seed = phnet_rng_seed(g.rng0);
+            gemm16<E>(xs, EP, g.Wa0, g.ba0, E, [&](int r, int n, float v) {
+                const long row = row0 + r;
+                float t = 0.f;
+                if (row < R) {
+                    const bool kept = !g.rng0.thresh || phnet_rng_keep(seed, phnet_rng_index(g.rng0, (uint64_t)row * E + n), g.rng0.thresh);
+                    t = g.resid[(size_t)row * E + n] + (kept ? v * p.scale : 0.f);
+                }
+                ts[r * EP + n] = t;
+            });
+        }
+        __syncthreads();
+        layernorm16<E>(ts, EP, g.ln0w, g.ln0b, g.eps0, xs, EP, nullptr, row0, (int)R);
+        __syncthreads();
+        gemm16<E>(xs, EP, g.Wq, g.bq, E, [&](int r, int n, float v) { fs[r * EP + n] = v; });
+    } else {
+        // ---- t and q as an earlier launch left them (rows past R: zeros) ----
+        for (int i = threadIdx.x; i < ROWS * (E / 4); i += NT) {
+            const int r = i / (E / 4), c4 = (i - r * (E / 4)) * 4;
+            f4 q = {0.f, 0.f, 0.f, 0.f}, t = {0.f, 0.f, 0.f, 0.f};
+            if (row0 + r < R) {
+                q = *reinterpret_cast<const f4*>(g.in + (size_t)(row0 + r) * E + c4);
+                t = *reinterpret_cast<const f4*>(g.resid + (size_t)(row0 + r) * E + c4);
+            }
+            *reinterpret_cast<f4*>(fs + r * EP + c4) = q;
+            *reinterpret_cast<f4*>(ts + r * EP + c4) = t;
+        }
+    }
+    __syncthreads();
+    // ---- cross-attention of the 16 rows x H heads into xs: the 4 rows of a wave share a head (LDS broadcast) ----
+    {
+        const uint64_t seed = phnet_rng_seed(g.rngC);
+        const int part = threadIdx.x % attn_dev::LPR;
+        for (int pair = threadIdx.x / attn_dev::LPR; pair < ROWS * H; pair += NT / attn_dev::LPR) {
+            const int r = pair % ROWS, h = pair / ROWS;
+            const bool live = row0 + r < R;
+            const int row = live ? (int)(blockIdx.x * ROWS + r) : 0;                 // within the item
+            float qr[attn_dev::D], out[attn_dev::D];
+            attn_dev::load_q_scaled(qr, fs + r * EP + h * attn_dev::D, g.qscale);
+            const uint64_t rbase = ((uint64_t)h * g.Lq + row) * Lk;
+            attn_dev::attn_row_head<EP, false>(qr, Ks + h * attn_dev::D, Vs + h * attn_dev::D, valid, Lk, part, nullptr, g.rngC, seed,
+                                               blockIdx.y, rbase, g.keep_scale, out);
+            if (part == 0)
+#pragma unroll
+                for (int d = 0; d < attn_dev::D; ++d) xs[r * EP + h * attn_dev::D + d] = live ? out[d] : 0.f;
+        }
+    }
+    __syncthreads();
+    // ---- chain B: t = t + dropout(attn @ Wa^T + ba) ----
+    {
+        const uint64_t seed = phnet_rng_seed(p.rngA);
+        gemm16<E>(xs, EP, p.Wa, p.ba, E, [&](int r, int n, float v) {
+            const long row = row0 + r;
+            float t = 0.f;
+            if (row < R) {
+                const bool kept = !p.rngA.thresh || phnet_rng_keep(seed, phnet_rng_index(p.rngA, (uint64_t)row * E + n), p.rngA.thresh);
+                t = ts[r * EP + n] + (kept ? v * p.scale : 0.f);
+            }
+            ts[r * EP + n] = t;
+        });
+    }
+    __syncthreads();
+    layernorm16<E>(ts, EP, p.ln1w, p.ln1b, p.eps, xs, EP, nullptr, row0, (int)R);
+    __syncthreads();
+    {   // f = dropout(gelu(h @ W1^T + b1))
+        const uint64_t seed = phnet_rng_seed(p.rngF);
+        gemm16<E>(xs, EP, p.W1, p.b1, FF, [&](int r, int n, float v) {
+            const long row = row0 + r;
+            const bool kept = !p.rngF.thresh || phnet_rng_keep(seed, phnet_rng_index(p.rngF, (uint64_t)row * FF + n), p.rngF.thresh);
+            fs[r * FP + n] = (row < R && kept) ? gelu_erf(v) * p.scale : 0.f;
+        });
+    }
+    __syncthreads();
+    {   // t = t + dropout(f @ W2^T + b2)
+        const uint64_t seed = phnet_rng_seed(p.rng3);
+        gemm16<FF>(fs, FP, p.W2, p.b2, E, [&](int r, int n, float v) {
+            const long row = row0 + r;
+            const bool kept = !p.rng3.thresh || phnet_rng_keep(seed, phnet_rng_index(p.rng3, (uint64_t)row * E + n), p.rng3.thresh);
+            ts[r * EP + n] += (row < R && kept) ? v * p.scale : 0.f;
+        });
+    }
+    __syncthreads();
+    layernorm16<E>(ts, EP, p.ln2w, p.ln2b, p.eps, xs, EP, p.h_out, row0, (int)R);
+    __syncthreads();
+    if (p.t_out)
+        for (int i = threadIdx.x; i < ROWS * (E / 4); i += NT) {
+            const int r = i / (E / 4), c4 = (i - r * (E / 4)) * 4;
+            if (row0 + r < R) *reinterpret_cast<f4*>(p.t_out + (size_t)(row0 + r) * E + c4) = *reinterpret_cast<const f4*>(ts + r * EP + c4);
+        }
+    if (p.Wg)
+        gemm16<E>(xs, EP, p.Wg, p.bg, p.NG, [&](int r, int n, float v) {
+            if (row0 + r < R) p.y_out[(size_t)(row0 + r) * p.NG + n] = v;
+        });
+}
+
 // ---- the towers of a branch + the lane prior update in one launch (forward only) ----------------------------------------------
 // Per tower t (cls / reg / offsets): h1 = relu(x @ W1_t^T + b1_t); h2 = relu(h1 @ W2_t^T + b2_t); head_t = h2 @ Wh_t^T + bh_t;
 // then the prior update of Router4OL.py:328-345 on (cls 2 | reg 4 | offsets S) - the arithmetic of lane_update_fwd_kernel
@@ -329,6 +485,51 @@ PHNET_API int phnet_rowchain_fwd(const float* in, const float* resid, const floa
         }
         hipLaunchKernelGGL((rowchain_kernel<256, 512, false>), grid, dim3(NT), lds, (hipStream_t)stream, p);
     } else return PHNET_ERR_ARG;
+    return phnet_launch_status();
+}
+
+// [chain A] -> cross-attention core -> [chain B] of a pre-norm decoder layer in one launch (rowchain_attn_kernel above): the bits of
+// phnet_rowchain_fwd -> phnet_attention_fwd -> phnet_rowchain_fwd.  B items as contiguous row blocks: item b owns rows
+// [b*Lq, (b+1)*Lq) of in / resid / the outputs and keys [b*Lk, (b+1)*Lk) of k / v (row strides sk / sv) / key_valid.
+// Chain A (Wa0 != NULL): in = the self-attention output, resid its residual, t = resid + dropout(in @ Wa0^T + ba0) [site call_a0],
+// q = LayerNorm(t; ln0w, ln0b, eps0) @ Wq^T + bq.  Without it: in = q and resid = t of an earlier launch.  Attention weights:
+// dropout site call_c with probability attn_drop_p.  Chain B = phnet_rowchain_fwd with the out-projection Wa / ba, the
+// feed-forward block (required) and the optional next projection Wg / bg [NG][E].
+// Supported: E = 128 (8 heads of width 16), FF = 256, 1 <= Lk <= 64; anything else returns PHNET_ERR_ARG and launches nothing.
+PHNET_API int phnet_rowchain_attn_fwd(const float* in, const float* resid, const float* Wa0, const float* ba0, const float* ln0w,
+                                      const float* ln0b, const float* Wq, const float* bq, float eps0,
+                                      const float* k, const float* v, int64_t sk, int64_t sv, const uint8_t* key_valid,
+                                      const float* Wa, const float* ba, const float* ln1w, const float* ln1b,
+                                      const float* W1, const float* b1, const float* W2, const float* b2, const float* ln2w, const float* ln2b,
+                                      const float* Wg, const float* bg, float* t_out, float* h_out, float* y_out,
+                                      int32_t B, int32_t Lq, int32_t Lk, int32_t H, int32_t E, int32_t FF, int32_t NG, float eps,
+                                      const uint64_t* rng_state, uint64_t call_a0, uint64_t call_c, uint64_t call_a, uint64_t call_f,
+                                      uint64_t call_3, float drop_p, float attn_drop_p, void* stream)
+{
+    if (B < 1 || Lq < 1 || NG < 0 || drop_p < 0.f || drop_p >= 1.f || attn_drop_p < 0.f || attn_drop_p >= 1.f) return PHNET_ERR_ARG;
+    if (E != 128 || FF != 256 || H * attn_dev::D != E || Lk < 1 || Lk > LKMAX || (int64_t)B * Lq > INT32_MAX) return PHNET_ERR_ARG;
+    if (!in || !resid || !k || !v || !Wa || !ba || !ln1w || !ln1b || !W1 || !b1 || !W2 || !b2 || !ln2w || !ln2b) return PHNET_ERR_ARG;
+    if (Wa0 && (!ba0 || !ln0w || !ln0b || !Wq || !bq)) return PHNET_ERR_ARG;
+    if (Wg && (!bg || !y_out || NG < 1)) return PHNET_ERR_ARG;
+    if (((uintptr_t)k & 15) || ((uintptr_t)v & 15) || (sk & 3) || (sv & 3) || sk < E || sv < E) return PHNET_ERR_ARG;      // float4 staging
+    if (((uintptr_t)in & 15) || ((uintptr_t)resid & 15) || ((uintptr_t)t_out & 15)) return PHNET_ERR_ARG;                  // float4 rows
+    const float scale = (rng_state && drop_p > 0.f) ? 1.0f / (1.0f - drop_p) : 1.0f;
+    const DropRng rngC = phnet_make_rng(rng_state, call_c, attn_drop_p);
+    RowChainAttn g{in, resid, Wa0, ba0, ln0w, ln0b, Wq, bq, k, v, key_valid,
+                   RowChain{nullptr, nullptr, Wa, ba, ln1w, ln1b, W1, b1, W2, b2, ln2w, ln2b, Wg, bg, t_out, h_out, y_out, B * Lq, NG, eps,
+                            phnet_make_rng(rng_state, call_a, drop_p), phnet_make_rng(rng_state, call_f, drop_p),
+                            phnet_make_rng(rng_state, call_3, drop_p), scale},
+                   (long)sk, (long)sv, Lq, Lk, eps0, 1.0f / sqrtf((float)attn_dev::D), rngC.thresh ? 1.0f / (1.0f - attn_drop_p) : 1.0f,
+                   phnet_make_rng(rng_state, call_a0, drop_p), rngC};
+    // LDS: the three row buffers of rowchain_kernel + K and V of all heads for Lk keys; at Lk = 64: 33.5 + 66 KB of the 160 KB a
+    // workgroup may take (a CU holds one such workgroup - the chain has at most 15 per item anyway)
+    constexpr size_t ROW_BYTES = (size_t)ROWS * (2 * (128 + 4) + (256 + 4)) * sizeof(float);
+    constexpr size_t MAX_BYTES = ROW_BYTES + (size_t)2 * LKMAX * (128 + 4) * sizeof(float);
+    static_assert(MAX_BYTES + LKMAX <= 160 * 1024, "rowchain_attn_kernel: LDS of one workgroup");
+    const size_t lds = ROW_BYTES + (size_t)2 * Lk * (128 + 4) * sizeof(float);
+    static bool attr = false;
+    if (!attr && !(attr = phnet_allow_dynamic_lds({(const void*)rowchain_attn_kernel<128, 256>}, (int)MAX_BYTES))) return PHNET_ERR_LAUNCH;
+    hipLaunchKernelGGL((rowchain_attn_kernel<128, 256>), dim3((unsigned)ceil_div64(Lq, ROWS), (unsigned)B), dim3(NT), lds, (hipStream_t)stream, g);
     return phnet_launch_status();
 }
 

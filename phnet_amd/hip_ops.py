@@ -1404,6 +1404,7 @@ def rowchain_fwd(x, resid=None, wa=None, ba=None, ln1=None, ffn=None, ln2=None, 
         ff = w1.shape[0]
     sites = [s for s in (rng_a, rng_f, rng_3) if s is not None]
     state, p = (sites[0][0], sites[0][2]) if sites else (None, 0.0)
+    assert all(s[2] == p and s[0].data_ptr() == state.data_ptr() for s in sites), "rowchain_fwd: the dropout sites of one launch share one counter and one probability"
 
     def call(rng, width):
         return 0 if rng is None else _rng_args(rng, width)[1]
@@ -1414,6 +1415,59 @@ def rowchain_fwd(x, resid=None, wa=None, ba=None, ln1=None, ffn=None, ln2=None, 
                                    _ptr(ln2[0]) if ln2 is not None else None, _ptr(ln2[1]) if ln2 is not None else None, _ptr(wg), _ptr(bg),
                                    _ptr(t), _ptr(h), _ptr(y), r, e, ff, ng, float(eps), _ptr(state), call(rng_a, e), call(rng_f, ff), call(rng_3, e),
                                    float(p), _stream()), "phnet_rowchain_fwd")
+    return t, h, y
+
+
+ROWCHAIN_ATTN_MAX_KEYS = 64       # csrc/rowchain.hip: LKMAX
+
+
+def rowchain_attn_ok(e: int, ff: int, heads: int, lk: int) -> bool:
+    """The shapes phnet_rowchain_attn_fwd takes (everything else: PHNET_ERR_ARG - the caller keeps the three launches)."""
+    return e == 128 and ff == 256 and heads * 16 == e and 1 <= lk <= ROWCHAIN_ATTN_MAX_KEYS
+
+
+def rowchain_attn_fwd(x, resid, k, v, heads: int, wa, ba, ln1, ffn, ln2, chain_a=None, key_valid=None, wg=None, bg=None,
+                      eps: float = 1e-5, eps_a: float = 1e-5, rng_a0=None, rng_c=None, rng_a=None, rng_f=None, rng_3=None,
+                      batch: int = 1, want_t: bool = True, want_h: bool = False, out=None):
+    """[chain A] -> cross-attention core -> [chain B] in one launch (csrc/rowchain.hip), forward only: the bits of
+    rowchain_fwd -> attention_fwd -> rowchain_fwd.  chain_a = (wa0, ba0, ln0w, ln0b, wq, bq): x [R,E] = the self-attention output,
+    resid its residual (dropout site rng_a0); chain_a = None: x = q and resid = t of an earlier launch.  k / v [batch*Lk, E] (any
+    row stride), key_valid u8[batch*Lk]; rng_c: dropout site of the attention weights.  The rest as rowchain_fwd with the
+    feed-forward block.  out = (t, h, y): caller-provided outputs (None entries are not produced).  -> (t, h, y)."""
+    _req(x, name="x"); _req(resid, name="resid")
+    r, e = x.shape
+    lq, lk = r // batch, k.shape[0] // batch
+    assert r == lq * batch and k.shape[0] == lk * batch and v.shape[0] == k.shape[0] and k.stride(1) == 1 and v.stride(1) == 1
+    dev = x.device
+    ng = wg.shape[0] if wg is not None else 0
+    if out is not None:
+        t, h, y = out
+    else:
+        t = torch.empty((r, e), dtype=torch.float32, device=dev) if want_t else None
+        h = torch.empty((r, e), dtype=torch.float32, device=dev) if want_h else None
+        y = torch.empty((r, ng), dtype=torch.float32, device=dev) if wg is not None else None
+    w1, b1, w2, b2 = ffn
+    ff = w1.shape[0]
+    a6 = tuple(chain_a) if chain_a is not None else (None,) * 6
+    for tns in a6 + (wa, ba, w1, b1, w2, b2, wg, bg, t, h, y) + tuple(ln1) + tuple(ln2):
+        if tns is not None:
+            _req(tns, name="rowchain operand")
+    if key_valid is not None:
+        _req(key_valid, torch.uint8, "key_valid")
+    sites = [s for s in (rng_a0, rng_a, rng_f, rng_3) if s is not None]
+    state, p = (sites[0][0], sites[0][2]) if sites else (None, 0.0)
+    if state is None and rng_c is not None:
+        state = rng_c[0]
+    assert all(s[2] == p for s in sites), "rowchain_attn_fwd: the dropout sites of the chains share one probability (rng_c has its own)"
+    assert all(s[0].data_ptr() == state.data_ptr() for s in sites + ([rng_c] if rng_c is not None else [])), "one dropout counter per launch"
+
+    def call(rng, width):
+        return 0 if rng is None else _rng_args(rng, width)[1]
+    check(lib().phnet_rowchain_attn_fwd(_ptr(x), _ptr(resid), *[_ptr(a) for a in a6], float(eps_a), _ptr(k), _ptr(v), k.stride(0), v.stride(0),
+                                        _ptr(key_valid), _ptr(wa), _ptr(ba), _ptr(ln1[0]), _ptr(ln1[1]), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                        _ptr(ln2[0]), _ptr(ln2[1]), _ptr(wg), _ptr(bg), _ptr(t), _ptr(h), _ptr(y), batch, lq, lk, heads, e, ff, ng,
+                                        float(eps), _ptr(state), call(rng_a0, e), call(rng_c, 0), call(rng_a, e), call(rng_f, ff), call(rng_3, e),
+                                        float(p), float(rng_c[2]) if rng_c is not None else 0.0, _stream()), "phnet_rowchain_attn_fwd")
     return t, h, y
 
 

@@ -204,13 +204,14 @@ class DetNetV2(nn.Module):
     def forward_first(self, decode_feat_l, priors):
         return self._branch(decode_feat_l, priors, False)
 
-    def forward_second(self, last_cut, attn_feat, stage, priors):
-        """attn_feat [N,1,128]; last_cut: None, a [M,1,128] tensor, or (tokens [M,1,128], valid bool[M]) with fixed M."""
+    def forward_second(self, last_cut, attn_feat, stage, priors, prefix=None):
+        """attn_feat [N,1,128]; last_cut: None, a [M,1,128] tensor, or (tokens [M,1,128], valid bool[M]) with fixed M.
+        prefix: this frame's rows of `transformer_Dec.decoder_prefix` (frames with a memory only)."""
         mask = None
         if isinstance(last_cut, tuple):
             last_cut, mask = last_cut
         if last_cut is not None and last_cut.shape[0] != 0:
-            feat = self.transformer_Dec(tgt=attn_feat, memory=last_cut, memory_key_valid=mask)
+            feat = self.transformer_Dec(tgt=attn_feat, memory=last_cut, memory_key_valid=mask, prefix=prefix)
         else:
             feat = attn_feat
         return self._branch(feat.reshape(1, self.num_priors, -1), priors, True)
@@ -540,6 +541,9 @@ class RouterOL(nn.Module, DeviceResults):
         # stage-major schedule only: branch B's passes run forward without autograd and their backward runs as ONE batch
         # (_BranchBDeferred); False: every pass is its own autograd sub-graph (same arithmetic, same dropout masks)
         self.defer_branch_b = True
+        # ... and layer 1 of their decoder up to its cross-attention (no memory in it) runs once per stage for frames 1..T-1 as a
+        # batch (TransformerDecoder.decoder_prefix) instead of once per pass; False: every pass runs its own
+        self.hoist_decoder_prefix = True
 
     @property
     def head(self):
@@ -737,10 +741,18 @@ class RouterOL(nn.Module, DeviceResults):
             tok_t = src.split(1, dim=0)
             pri_t = pri_src.split(1, dim=0) if pri_src.requires_grad else [pri_src[t:t + 1] for t in range(T)]
             lines_b, preds_b = [], []
+            prefix = None
+            if defer and self.hoist_decoder_prefix and T > 1:
+                # the passes of frames 1..T-1 as items stage*(T-1) .. of one batch: the masks each pass would have drawn itself
+                with torch.no_grad(), PF.DropoutStream.items(BRANCH_B_SITES, stage * (T - 1), N):
+                    tgt = src[1:].reshape((T - 1) * N, E)
+                    if det.transformer_Dec._can_fuse(tgt, ring):
+                        prefix = [r.view(T - 1, N, E) for r in det.transformer_Dec.decoder_prefix(tgt, batch=T - 1)]
             for t in range(T):
                 mem = (ring[t:t + W].view(-1, 1, E), ring_valid[t:t + W].view(-1)) if t > 0 else None
                 with torch.set_grad_enabled(not defer), PF.DropoutStream.items(BRANCH_B_SITES, stage * (T - 1) + t - 1 if t else 0, 0):
-                    pred_b, line_b = det.forward_second(mem, tok_t[t].transpose(0, 1), stage, pri_t[t])
+                    pred_b, line_b = det.forward_second(mem, tok_t[t].transpose(0, 1), stage, pri_t[t],
+                                                        None if prefix is None or t == 0 else (prefix[0][t - 1], prefix[1][t - 1]))
                 preds_b.append(pred_b)
                 lines_b.append(line_b.detach())
                 if t == T - 1:

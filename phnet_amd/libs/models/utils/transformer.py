@@ -66,43 +66,90 @@ class TransformerDecoder(nn.Module):
         self.return_intermediate = return_intermediate
 
     fuse_row_chains = True      # no-autograd forward: the row-local chains between the attention cores as single launches
+    # ... and the cross-attention core as a stage of the chain around it (rowchain_attn_kernel) instead of its own launch.  Off:
+    # measured slower - the stage runs the (row, head) pairs of 8 attention workgroups on the one CU that owns the 16 rows and is
+    # bound by that CU's VALU: the one launch takes 5.4 / 8.0 us longer than the launches it replaces (the stand-alone core runs
+    # 5 us on 120 CUs, and a launch boundary inside a replayed graph costs about 0.1 us), +0.14 ms per training step
+    fuse_cross_attention = False
 
-    def _forward_row_chains(self, x: torch.Tensor, mem: torch.Tensor, memory_key_valid, batch: int) -> torch.Tensor:
+    def decoder_prefix(self, x: torch.Tensor, batch: int = 1):
+        """Layer 1 up to its cross-attention: [LayerNorm + q|k|v] -> self-attention core -> [out-projection + residual/dropout +
+        LayerNorm + q projection] for x [batch*L,E].  None of it looks at the memory, so a caller that has the targets of several
+        passes at hand runs it once for all of them and hands each pass its rows of (t, q) (`forward(..., prefix=)`).  Draws the
+        first two dropout sites of the decoder.  Only where `_can_fuse` holds."""
+        from phnet_amd import hip_ops as K
+        site = PF.DropoutStream.site
+        dev, first = x.device, self.layers[0]
+        tr, e = first.training, x.shape[1]
+        sa, ca = first.self_attn, first.multihead_attn
+        x = x.contiguous()
+        _, _, qkv = K.rowchain_fwd(x, ln1=(first.norm1.weight, first.norm1.bias), wg=sa.in_proj_weight, bg=sa.in_proj_bias,
+                                   eps=first.norm1.eps, want_t=False)
+        a, _ = K.attention_fwd(qkv[:, :e], qkv[:, e:2 * e], qkv[:, 2 * e:], sa.num_heads, None, rng=site(dev, sa.dropout if tr else 0.0),
+                               batch=batch)
+        t, _, q = K.rowchain_fwd(a, resid=x, wa=sa.out_proj.weight, ba=sa.out_proj.bias, ln1=(first.norm2.weight, first.norm2.bias),
+                                 wg=ca.in_proj_weight[:e], bg=ca.in_proj_bias[:e], eps=first.norm2.eps,
+                                 rng_a=site(dev, first.dropout1.p if tr else 0.0))
+        return t, q
+
+    def _forward_row_chains(self, x: torch.Tensor, mem: torch.Tensor, memory_key_valid, batch: int, prefix=None) -> torch.Tensor:
         """The same decoder with every row-local chain of a layer in one launch (csrc/rowchain.hip): per layer
-        [LayerNorm + q|k|v projection] -> self-attention core -> [out-projection + residual/dropout + LayerNorm + q projection]
-        -> cross-attention core -> [out-projection + residual/dropout + LayerNorm + feed-forward + residual/dropout + the next
-        LayerNorm (+ the next layer's q|k|v projection)]: 5 launches + the memory's k|v projection instead of 13.  Forward only;
-        dropout sites are drawn in the order of `TransformerDecoderLayer.forward`, so a recomputation through the unfused
-        kernels sees the same masks."""
+        [LayerNorm + q|k|v projection] -> self-attention core -> [out-projection + residual/dropout + LayerNorm + q projection
+        -> cross-attention core -> out-projection + residual/dropout + LayerNorm + feed-forward + residual/dropout + the next
+        LayerNorm (+ the next layer's q|k|v projection)]: 5 launches + the memory's k|v projection instead of 13; the bracket
+        around the cross-attention is three launches, or one with `fuse_cross_attention` where it applies (rowchain_attn_kernel:
+        E = 128, <= 64 keys).  prefix = (t, q) of `decoder_prefix` for these rows: layer 1 then starts at its cross-attention.
+        Forward only; dropout sites are drawn in the order of `TransformerDecoderLayer.forward`, so a recomputation through the
+        unfused kernels sees the same masks."""
         from phnet_amd import hip_ops as K
         site = PF.DropoutStream.site
         dev = x.device
         x = x.contiguous()
         first = self.layers[0]
         e = x.shape[1]
-        _, _, qkv = K.rowchain_fwd(x, ln1=(first.norm1.weight, first.norm1.bias), wg=first.self_attn.in_proj_weight,
-                                   bg=first.self_attn.in_proj_bias, eps=first.norm1.eps, want_t=False)
+        lk = mem.shape[0] // batch
+        kvu8 = None if memory_key_valid is None else memory_key_valid.contiguous().view(torch.uint8)
+        qkv = None
+        if prefix is None:
+            _, _, qkv = K.rowchain_fwd(x, ln1=(first.norm1.weight, first.norm1.bias), wg=first.self_attn.in_proj_weight,
+                                       bg=first.self_attn.in_proj_bias, eps=first.norm1.eps, want_t=False)
         h = None
         for i, layer in enumerate(self.layers):
             tr = layer.training
             p_of = lambda d: d.p if tr else 0.0                                           # noqa: E731
             sa, ca = layer.self_attn, layer.multihead_attn
-            a, _ = K.attention_fwd(qkv[:, :e], qkv[:, e:2 * e], qkv[:, 2 * e:], sa.num_heads, None,
-                                   rng=site(dev, sa.dropout if tr else 0.0), batch=batch)
-            t, _, q = K.rowchain_fwd(a, resid=x, wa=sa.out_proj.weight, ba=sa.out_proj.bias, ln1=(layer.norm2.weight, layer.norm2.bias),
-                                     wg=ca.in_proj_weight[:e], bg=ca.in_proj_bias[:e], eps=layer.norm2.eps, rng_a=site(dev, p_of(layer.dropout1)))
+            r_sa, r_1 = site(dev, sa.dropout if tr else 0.0), site(dev, p_of(layer.dropout1))    # (drawn by decoder_prefix: same ids)
+            chain_a = dict(wa=sa.out_proj.weight, ba=sa.out_proj.bias, ln1=(layer.norm2.weight, layer.norm2.bias),
+                           wg=ca.in_proj_weight[:e], bg=ca.in_proj_bias[:e], eps=layer.norm2.eps)
+            a = t = q = None
+            if i == 0 and prefix is not None:
+                t, q = prefix
+            else:
+                a, _ = K.attention_fwd(qkv[:, :e], qkv[:, e:2 * e], qkv[:, 2 * e:], sa.num_heads, None, rng=r_sa, batch=batch)
             kv = K.linear_fwd(mem, ca.in_proj_weight[e:], ca.in_proj_bias[e:])
-            kvu8 = None if memory_key_valid is None else memory_key_valid.contiguous().view(torch.uint8)
-            a2, _ = K.attention_fwd(q, kv[:, :e], kv[:, e:], ca.num_heads, kvu8, rng=site(dev, ca.dropout if tr else 0.0), batch=batch)
+            r_c = site(dev, ca.dropout if tr else 0.0)
             nxt = self.layers[i + 1] if i + 1 < len(self.layers) else None
             norm = nxt.norm1 if nxt is not None else self.norm
             r_a, r_f, r_3 = site(dev, p_of(layer.dropout2)), site(dev, p_of(layer.dropout)), site(dev, p_of(layer.dropout3))
-            x, h, qkv = K.rowchain_fwd(a2, resid=t, wa=ca.out_proj.weight, ba=ca.out_proj.bias, ln1=(layer.norm3.weight, layer.norm3.bias),
-                                       ffn=(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias),
-                                       ln2=(norm.weight, norm.bias) if norm is not None else (layer.norm3.weight, layer.norm3.bias),
-                                       wg=None if nxt is None else nxt.self_attn.in_proj_weight,
-                                       bg=None if nxt is None else nxt.self_attn.in_proj_bias, eps=layer.norm3.eps,
-                                       rng_a=r_a, rng_f=r_f, rng_3=r_3, want_t=True, want_h=nxt is None)
+            chain_b = dict(wa=ca.out_proj.weight, ba=ca.out_proj.bias, ln1=(layer.norm3.weight, layer.norm3.bias),
+                           ffn=(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias),
+                           ln2=(norm.weight, norm.bias) if norm is not None else (layer.norm3.weight, layer.norm3.bias),
+                           wg=None if nxt is None else nxt.self_attn.in_proj_weight,
+                           bg=None if nxt is None else nxt.self_attn.in_proj_bias, eps=layer.norm3.eps,
+                           rng_a=r_a, rng_f=r_f, rng_3=r_3, want_t=True, want_h=nxt is None)
+            if self.fuse_cross_attention and K.rowchain_attn_ok(e, layer.linear1.out_features, ca.num_heads, lk):
+                if a is not None:
+                    x, h, qkv = K.rowchain_attn_fwd(a, x, kv[:, :e], kv[:, e:], ca.num_heads, key_valid=kvu8, rng_c=r_c, rng_a0=r_1, batch=batch,
+                                                    chain_a=(chain_a["wa"], chain_a["ba"], *chain_a["ln1"], chain_a["wg"], chain_a["bg"]),
+                                                    eps_a=chain_a["eps"], **chain_b)
+                else:
+                    x, h, qkv = K.rowchain_attn_fwd(q.contiguous(), t.contiguous(), kv[:, :e], kv[:, e:], ca.num_heads, key_valid=kvu8,
+                                                    rng_c=r_c, batch=batch, **chain_b)
+                continue
+            if a is not None:
+                t, _, q = K.rowchain_fwd(a, resid=x, rng_a=r_1, **chain_a)
+            a2, _ = K.attention_fwd(q, kv[:, :e], kv[:, e:], ca.num_heads, kvu8, rng=r_c, batch=batch)
+            x, h, qkv = K.rowchain_fwd(a2, resid=t, **chain_b)
         return h if self.norm is not None else x
 
     def _can_fuse(self, x, mem) -> bool:
@@ -113,13 +160,16 @@ class TransformerDecoder(nn.Module):
                 and l0.self_attn.embed_dim // l0.self_attn.num_heads in (16, 32) and len(ps) == 1 and self.norm is not None
                 and (e == 128 or not self.training))
 
-    def forward(self, tgt: torch.Tensor, memory: torch.Tensor, memory_key_valid=None, batch: int = 1) -> torch.Tensor:
+    def forward(self, tgt: torch.Tensor, memory: torch.Tensor, memory_key_valid=None, batch: int = 1, prefix=None) -> torch.Tensor:
         """tgt [L,1,E] or [L,E]; memory [M,1,E] or [M,E]; memory_key_valid bool[M]; returns the same rank as tgt.
-        batch = B: tgt [B*L,E], memory [B*M,E], mask [B*M] hold B clips as contiguous row blocks."""
+        batch = B: tgt [B*L,E], memory [B*M,E], mask [B*M] hold B clips as contiguous row blocks.
+        prefix: the rows of `decoder_prefix` that belong to tgt (the caller checked `_can_fuse`)."""
         shape = tgt.shape
         x, mem = tgt.reshape(-1, shape[-1]), memory.reshape(-1, memory.shape[-1])
         if self._can_fuse(x, mem):
-            return self._forward_row_chains(x, mem.contiguous(), memory_key_valid, batch).reshape(shape)
+            return self._forward_row_chains(x, mem.contiguous(), memory_key_valid, batch, prefix).reshape(shape)
+        if prefix is not None:
+            raise RuntimeError("TransformerDecoder: a decoder_prefix needs the row-chain forward")
         h = None
         for i, layer in enumerate(self.layers):
             nxt = self.layers[i + 1].norm1 if i + 1 < len(self.layers) else self.norm
