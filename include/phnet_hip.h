@@ -243,6 +243,19 @@ uint64_t phnet_conv3p_stats_blocks(int64_t M, int32_t Ca, int32_t Nn, uint64_t w
 int phnet_conv3p_fwd(const float* x, const void* packed, const float* bias, const float* addend, float* y, float* stats,
                      int32_t N, int32_t H, int32_t W, int32_t Ca, int32_t Nn, int32_t relu,
                      void* workspace, uint64_t ws_bytes, void* stream);
+/* ---- Linear layers over MANY rows on tall tiles (csrc/linrows.hip): the hyper-network of utils/dynamic_head.py:31-59 with the frames
+ * of a clip batched.  phnet_linrows_fwd: y [M][N] = x [M][K] * w [N][K]^T (+ bias) (ReLU); phnet_linrows_dgrad: dx [M][N] = dy [M][K] *
+ * w [K][N] (w as the forward holds it).  Results are phnet_conv2d_fwd's / phnet_conv2d_dgrad's on the [M][1][1][K] image BIT FOR BIT,
+ * split-K factor and workspace use included; arithmetic mode 3 only, K % 16 == 0, N % 4 == 0, operands below 2 GB (else
+ * PHNET_ERR_ARG).  phnet_linrows_applies: 1 where phnet_amd.hip_ops runs these instead of the generic kernel - the shape class measured
+ * faster on MI355X (more than 256 rows, one round of 256 workgroups; never under phnet_tune_force_k_tile(-300)). */
+int phnet_linrows_applies(int64_t M, int32_t K, int32_t N, int32_t dgrad);
+int phnet_linrows_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t K, int32_t N, int32_t relu,
+                      void* workspace, uint64_t ws_bytes, void* stream);
+int phnet_linrows_dgrad(const float* dy, const float* w, float* dx, int64_t M, int32_t K, int32_t N, void* workspace,
+                        uint64_t ws_bytes, void* stream);
+int phnet_linrows_kernel(int64_t M, int32_t K, int32_t N, int32_t dgrad, uint64_t ws_bytes, char* name, int32_t name_cap,
+                         int32_t* splits);
 /* host-side queries (no device work, callable without a GPU; HOST pointers), answered by the decision functions the launches
  * call.  phnet_conv2d_plan: tile, split-K factor and K-tile depth of a forward GEMM of M x Co x K (M < 2^31).  phnet_*_kernel:
  * the instantiation the launch entry of the same shape arguments runs, as rocprofv3 spells it after the namespace (e.g.

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include "conv_igemm.h"
 #include "tuning.h"
+#include "linrows.h"
 
 using namespace igemm;
 
@@ -329,7 +330,9 @@ TileChoice pick_tile(long M, long N)
     // matters is the number of co-resident workgroups per CU, not the tile's arithmetic intensity: 64x64 tiles with
     // the block count topped up to ~1250 by split-K beat the larger tiles on every trunk layer (72-80 us vs 85-130 us).
     const int mma = tuning().mma_mode;
-    if (mma == 3 && M <= 2048) return {64, 64};                 // (64x64 is the fastest tile up to the 1200 rows of a batched clip)
+    // (64x64 is the fastest tile of THIS kernel up to the 1200 rows of a batched clip; the Linear layers of that size whose launch
+    // fits one round of tall tiles leave for linrows.hip before they get here, hip_ops.linear_fwd / linear_dgrad)
+    if (mma == 3 && M <= 2048) return {64, 64};
     if (mma >= 1) {
         // split-bf16: the loop is bound by the operand split (VALU) and the LDS reads per MFMA, both of which shrink with
         // the wave tile - problems with enough tiles take the larger ones (bench_conv.py --mma --clips 8: 128x128 is
@@ -426,6 +429,13 @@ int conv_kernel_name(const ConvPick& p, char* name, int cap)
         else PHNET_LAUNCH_CONV___(DGRAD_, BM_, BN_, BKT_, UNI_, 1);                                                     \
     } while (0)
 
+// K range of one split of a pick: whole K tiles, the same number for every split (the last one takes what is left)
+int k_per_split_of(const ConvPick& p, int K)
+{
+    const int ksteps = (K + p.bkt - 1) / p.bkt;
+    return ((ksteps + p.splits - 1) / p.splits) * p.bkt;
+}
+
 template <bool DGRAD>
 int launch_conv(const float* X, const float* W, const float* bias, const float* addend, float* out, float* workspace,
                 size_t ws_bytes, ConvShape g, int relu, hipStream_t st, float* stats = nullptr)
@@ -437,12 +447,11 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
     g.splits = splits;
     float* dst = splits > 1 ? workspace : out;
     dim3 grid((unsigned)p.tiles, 1, (unsigned)splits);
-    const int ksteps = (K + p.bkt - 1) / p.bkt;
     // ceil, so the last split can come out short or - with the 64-deep tile, where ksteps < splits * (splits - 1) happens (240 x
     // 1856 -> 2880: 29 steps, 7 splits of 5) - EMPTY: its workgroups skip the K loop and write zeros to their slice of the
     // partial sums (tests/gemm_cases.py "empty_split").  With 16-deep tiles plan_conv keeps >= 256 of K = 16 steps per split
     // and splits <= 8, so ksteps >= 16 * splits > splits * (splits - 1): no empty split there
-    g.k_per_split = ((ksteps + splits - 1) / splits) * p.bkt;
+    g.k_per_split = k_per_split_of(p, K);
     if (p.taps3) {
         const int units = 3 * (g.Ci / 16);
         // in units for this kernel.  The last split can be short (15 units over 2 splits), never empty: K / splits >= 256
@@ -467,6 +476,24 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
 }
 
 }  // namespace
+
+// ---- what csrc/linrows.hip takes from here (linrows.h): the split of the reduction the generic kernel would run a Linear layer
+// with, and the reduce launch - so that its partial sums group exactly as the generic kernel's ----
+ConvSplit phnet_linear_split(long M, int K, int N, bool dgrad, bool has_ws, size_t ws_bytes)
+{
+    ConvShape g;
+    if (dgrad) dgrad_shape((int)M, 1, 1, N, K, 1, 1, 1, 0, &g);
+    else fwd_shape((int)M, 1, 1, K, N, 1, 1, 1, 0, &g);
+    const ConvPick p = pick_conv(g, dgrad, has_ws, ws_bytes);
+    return ConvSplit{p.splits, k_per_split_of(p, K)};
+}
+
+void phnet_splitk_reduce(const float* part, float* out, const float* bias, long M, int N, int splits, int relu, hipStream_t st)
+{
+    const long total4 = M * N / 4;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)ceil_div64(total4, 256)), dim3(256), 0, st,
+                       part, out, bias, (const float*)nullptr, total4, N, splits, relu, 0, (float*)nullptr);
+}
 
 // Which tile / split-K factor / K tile phnet_conv2d_fwd runs a GEMM of M x Co x K with (a 1x1 convolution of K channels over M
 // pixels; M < 2^31).  Answered by the pick_conv the launch itself calls.

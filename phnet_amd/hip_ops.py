@@ -291,15 +291,43 @@ def conv2d_wgrad(dy, x, w_shape, stride: int, pad: int, dw: Optional[torch.Tenso
     return dw
 
 
+def linrows_applies(m: int, k: int, n: int, dgrad: bool) -> bool:
+    """Does the tall-tile kernel of csrc/linrows.hip take this Linear layer?  (m rows, reduction depth k, n output columns)"""
+    return bool(lib().phnet_linrows_applies(int(m), int(k), int(n), int(dgrad)))
+
+
+def _linrows(dgrad: bool, a2d, w, bias, relu: bool, n: int):
+    """a2d [M,K] -> [M,n] on csrc/linrows.hip: the generic kernel's result bit for bit, with the split-K scratch conv2d_fwd /
+    conv2d_dgrad would hand the same output."""
+    _req(a2d, name="x"); _req(w, name="w")
+    m, k = a2d.shape
+    out = torch.empty((m, n), dtype=torch.float32, device=a2d.device)
+    need = 8 * m * n * 4 if m * n < (1 << 23) else 0
+    ws = workspace(need, a2d.device) if need else None
+    if dgrad:
+        launch = lambda: check(lib().phnet_linrows_dgrad(_ptr(a2d), _ptr(w), _ptr(out), m, k, n, _ptr(ws), need, _stream()),
+                               "phnet_linrows_dgrad")
+    else:
+        launch = lambda: check(lib().phnet_linrows_fwd(_ptr(a2d), _ptr(w), _ptr(bias), _ptr(out), m, k, n, int(relu), _ptr(ws), need,
+                                                       _stream()), "phnet_linrows_fwd")
+    _timed_launch(lambda: _kernel(lib().phnet_linrows_kernel, m, k, n, int(dgrad), need), 2.0 * m * n * k, launch,
+                  shape=("dgrad" if dgrad else "fwd", m, n, k, 1), nbytes=4.0 * (m * k + m * n + n * k))
+    return out
+
+
 def linear_fwd(x2d, w, bias, relu: bool = False):
     """x [M,K], w [N,K] -> [M,N] (= conv 1x1 on an [M,1,1,K] image)."""
     m, k = x2d.shape
+    if linrows_applies(m, k, w.shape[0], False):
+        return _linrows(False, x2d, w, bias, relu, w.shape[0])
     return conv2d_fwd(x2d.view(m, 1, 1, k), w.view(w.shape[0], 1, 1, k), bias, 1, 0, relu).view(m, w.shape[0])
 
 
 def linear_dgrad(dy2d, w):
     m, n = dy2d.shape
     k = w.shape[1]
+    if linrows_applies(m, n, k, True):
+        return _linrows(True, dy2d, w, None, False, k)
     return conv2d_dgrad(dy2d.view(m, 1, 1, n), w.view(n, 1, 1, k), (1, 1), 1, 0).view(m, k)
 
 
@@ -1727,7 +1755,8 @@ def mask_metric_counts(pred, gt, radius: int, out=None):
 
 
 def tune_k_tile(code: int) -> None:
-    """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on."""
+    """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on,
+    -300 / -301 the tall-tile kernel of the many-row Linear layers (csrc/linrows.hip)."""
     check(lib().phnet_tune_force_k_tile(code), "phnet_tune_force_k_tile")
 
 
