@@ -209,7 +209,9 @@ int phnet_roi_pool_bwd(const float* dout, const float* fmap, const float* xs, co
 /* ---- convolution / linear on fp32 MFMA: replaces F.conv2d (libs/models/resnet.py:79-95,293-307;
  * libs/models/fpn.py:109-163) and F.linear (Router4OL.py:308-392, utils/dynamic_head.py:31-59, Router.py:72-81).
  * x [N][Hi][Wi][Ci], w [Co][R][S][Ci], bias [Co] or NULL, y [N][Ho][Wo][Co]; Ci%4==0, Co%4==0.
- * workspace optional (split-K partial sums; recommended: >= 16*N*Ho*Wo*Co*4 bytes for small grids). */
+ * workspace optional (split-K partial sums; the plan splits only as far as ws_bytes holds splits * N*Ho*Wo*Co*4.  What
+ * phnet_amd.hip_ops.splitk_workspace_bytes hands every launch: 8 slabs of the output where it has fewer than 2^23 elements, else none).
+ * A Linear layer ([M][1][1][K] image, 1x1 filter) of many rows runs on the tall tiles of csrc/linrows.hip where that is faster, same bits. */
 int phnet_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,
                      int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S,
                      int32_t stride, int32_t pad, int32_t relu, void* workspace, uint64_t ws_bytes, void* stream);
@@ -243,24 +245,12 @@ uint64_t phnet_conv3p_stats_blocks(int64_t M, int32_t Ca, int32_t Nn, uint64_t w
 int phnet_conv3p_fwd(const float* x, const void* packed, const float* bias, const float* addend, float* y, float* stats,
                      int32_t N, int32_t H, int32_t W, int32_t Ca, int32_t Nn, int32_t relu,
                      void* workspace, uint64_t ws_bytes, void* stream);
-/* ---- Linear layers over MANY rows on tall tiles (csrc/linrows.hip): the hyper-network of utils/dynamic_head.py:31-59 with the frames
- * of a clip batched.  phnet_linrows_fwd: y [M][N] = x [M][K] * w [N][K]^T (+ bias) (ReLU); phnet_linrows_dgrad: dx [M][N] = dy [M][K] *
- * w [K][N] (w as the forward holds it).  Results are phnet_conv2d_fwd's / phnet_conv2d_dgrad's on the [M][1][1][K] image BIT FOR BIT,
- * split-K factor and workspace use included; arithmetic mode 3 only, K % 16 == 0, N % 4 == 0, operands below 2 GB (else
- * PHNET_ERR_ARG).  phnet_linrows_applies: 1 where phnet_amd.hip_ops runs these instead of the generic kernel - the shape class measured
- * faster on MI355X (more than 256 rows, one round of 256 workgroups; never under phnet_tune_force_k_tile(-300)). */
-int phnet_linrows_applies(int64_t M, int32_t K, int32_t N, int32_t dgrad);
-int phnet_linrows_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t K, int32_t N, int32_t relu,
-                      void* workspace, uint64_t ws_bytes, void* stream);
-int phnet_linrows_dgrad(const float* dy, const float* w, float* dx, int64_t M, int32_t K, int32_t N, void* workspace,
-                        uint64_t ws_bytes, void* stream);
-int phnet_linrows_kernel(int64_t M, int32_t K, int32_t N, int32_t dgrad, uint64_t ws_bytes, char* name, int32_t name_cap,
-                         int32_t* splits);
 /* host-side queries (no device work, callable without a GPU; HOST pointers), answered by the decision functions the launches
  * call.  phnet_conv2d_plan: tile, split-K factor and K-tile depth of a forward GEMM of M x Co x K (M < 2^31).  phnet_*_kernel:
  * the instantiation the launch entry of the same shape arguments runs, as rocprofv3 spells it after the namespace (e.g.
  * "conv_igemm_kernel<64, 64, false, 16, true, 3, 4, true>"; name_cap bytes), and its split factor.  phnet_conv2d_kernel:
- * dgrad = 0 names phnet_conv2d_fwd / _fwd_fused, 1 phnet_conv2d_dgrad; ws_bytes = 0 = no workspace. */
+ * dgrad = 0 names phnet_conv2d_fwd / _fwd_fused, 1 phnet_conv2d_dgrad; ws_bytes = 0 = no workspace.  It names the launch WITHOUT
+ * addend and stats: a Linear layer that has one runs conv_igemm_kernel where the query says linrows_kernel (the only difference). */
 int phnet_conv2d_plan(int64_t M, int32_t Co, int32_t K, uint64_t ws_bytes, int32_t* bm, int32_t* bn, int32_t* splits,
                       int32_t* k_tile);
 int phnet_conv2d_kernel(int32_t dgrad, int32_t N, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t R, int32_t S,

@@ -15,8 +15,11 @@ extern "C" {
 int phnet_tune_force_conv_tile(int32_t bm, int32_t bn, int32_t splits);
 int phnet_tune_force_k_tile(int32_t k_tile);   /* 0 = heuristic, else 16 | 32 | 64; -1 / -2: uniform-tap kernel variant off / on;
                                                   -5 / -6: three-taps 3x3 stride-1 forward / dgrad kernel off / on;
-                                                  -300 / -301: tall-tile kernel of the many-row Linear layers (csrc/linrows.hip,
-                                                  phnet_linrows_applies) off / on */
+                                                  -300 / -301: tall-tile kernel of the many-row Linear layers (csrc/linrows.hip) off /
+                                                  on for the shape class it was measured faster at; -302: on for every Linear-shaped
+                                                  phnet_conv2d_fwd / _dgrad launch without addend / statistics that it can run (arithmetic
+                                                  mode 3, K % 16 == 0, operands below 2 GB), whatever the rows, columns, depth, forced tile
+                                                  or forced K tile - how tests reach it at small shapes */
 int phnet_tune_wgrad(int32_t allow_bm128, int32_t target_blocks);   /* wgrad tile / split-K policy; bits of the first argument:
                                                                         1 = no few-rows Linear kernel, 3 = no three-taps 3x3 kernel,
                                                                         4 = its 32-pixel steps, 5 = no producer / consumer variant

@@ -331,7 +331,7 @@ TileChoice pick_tile(long M, long N)
     // the block count topped up to ~1250 by split-K beat the larger tiles on every trunk layer (72-80 us vs 85-130 us).
     const int mma = tuning().mma_mode;
     // (64x64 is the fastest tile of THIS kernel up to the 1200 rows of a batched clip; the Linear layers of that size whose launch
-    // fits one round of tall tiles leave for linrows.hip before they get here, hip_ops.linear_fwd / linear_dgrad)
+    // fits one round of tall tiles keep this plan's split count and leave for linrows.hip in pick_conv)
     if (mma == 3 && M <= 2048) return {64, 64};
     if (mma >= 1) {
         // split-bf16: the loop is bound by the operand split (VALU) and the LDS reads per MFMA, both of which shrink with
@@ -384,7 +384,8 @@ ConvPlan plan_conv(long M, int Co, int K, bool has_ws, size_t ws_bytes)
     return p;
 }
 
-ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes)
+// extras: the launch has an addend or a statistics output (the host-only queries name the launch without them)
+ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes, bool extras)
 {
     const Tuning& tn = tuning();
     const long M = (long)g.N * g.Ho * g.Wo;
@@ -402,6 +403,12 @@ ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes)
     p.buf = p.uni && g.in_dil == 1 && tn.buf_loads && p.mma == 3;
     p.taps3 = tn.taps3 && p.buf && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Ho == g.Hi && g.Wo == g.Wi &&
               p.bkt == 16 && p.pf == 4 && g.Wi >= 2 && M * (long)g.Ci * 4 < 0x7fffffffL && (long)g.Co * K * 4 < 0x7fffffffL;
+    // a Linear layer without epilogue extras: the tall-tile kernel where it applies to this plan's split count (linrows.hip)
+    const bool linear = g.R == 1 && g.S == 1 && g.Hi == 1 && g.Wi == 1 && g.stride == 1 && g.pad == 0 && g.in_dil == 1;
+    if (linear && !extras && (p.rows = linrows_wm(M, K, g.Co, p.splits)) != 0) {
+        p.bm = 160 * p.rows; p.bn = 128;
+        p.tiles = ceil_div64(M, p.bm) * ceil_div64(g.Co, p.bn);
+    }
     return p;
 }
 
@@ -409,7 +416,8 @@ ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes)
 int conv_kernel_name(const ConvPick& p, char* name, int cap)
 {
     static const char* const tf[2] = {"false", "true"};
-    const int n = p.taps3 ? snprintf(name, (size_t)cap, "conv3x3s1_kernel<%s>", tf[p.dgrad])
+    const int n = p.rows  ? snprintf(name, (size_t)cap, LINROWS_NAME, tf[p.dgrad], p.rows)
+                : p.taps3 ? snprintf(name, (size_t)cap, "conv3x3s1_kernel<%s>", tf[p.dgrad])
                           : snprintf(name, (size_t)cap, "conv_igemm_kernel<%d, %d, %s, %d, %s, %d, %d, %s>", p.bm, p.bn, tf[p.dgrad], p.bkt,
                                      tf[p.uni], p.mma, p.pf, tf[p.buf]);
     return n < cap ? PHNET_OK : PHNET_ERR_ARG;
@@ -440,7 +448,7 @@ template <bool DGRAD>
 int launch_conv(const float* X, const float* W, const float* bias, const float* addend, float* out, float* workspace,
                 size_t ws_bytes, ConvShape g, int relu, hipStream_t st, float* stats = nullptr)
 {
-    const ConvPick p = pick_conv(g, DGRAD, workspace != nullptr, ws_bytes);
+    const ConvPick p = pick_conv(g, DGRAD, workspace != nullptr, ws_bytes, addend != nullptr || stats != nullptr);
     const long M = (long)g.N * g.Ho * g.Wo;
     const int K = g.R * g.S * g.Ci;
     const int splits = p.splits;
@@ -452,7 +460,9 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
     // partial sums (tests/gemm_cases.py "empty_split").  With 16-deep tiles plan_conv keeps >= 256 of K = 16 steps per split
     // and splits <= 8, so ksteps >= 16 * splits > splits * (splits - 1): no empty split there
     g.k_per_split = k_per_split_of(p, K);
-    if (p.taps3) {
+    if (p.rows) {
+        if (!linrows_launch(DGRAD, p.rows, X, W, bias, dst, M, K, g.Co, splits, g.k_per_split, relu, st)) return PHNET_ERR_LAUNCH;
+    } else if (p.taps3) {
         const int units = 3 * (g.Ci / 16);
         // in units for this kernel.  The last split can be short (15 units over 2 splits), never empty: K / splits >= 256
         // (plan_conv) is units >= 5.34 * splits, and units < splits * (splits - 1) would then need splits > 6 - at 7 and 8
@@ -477,24 +487,6 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
 
 }  // namespace
 
-// ---- what csrc/linrows.hip takes from here (linrows.h): the split of the reduction the generic kernel would run a Linear layer
-// with, and the reduce launch - so that its partial sums group exactly as the generic kernel's ----
-ConvSplit phnet_linear_split(long M, int K, int N, bool dgrad, bool has_ws, size_t ws_bytes)
-{
-    ConvShape g;
-    if (dgrad) dgrad_shape((int)M, 1, 1, N, K, 1, 1, 1, 0, &g);
-    else fwd_shape((int)M, 1, 1, K, N, 1, 1, 1, 0, &g);
-    const ConvPick p = pick_conv(g, dgrad, has_ws, ws_bytes);
-    return ConvSplit{p.splits, k_per_split_of(p, K)};
-}
-
-void phnet_splitk_reduce(const float* part, float* out, const float* bias, long M, int N, int splits, int relu, hipStream_t st)
-{
-    const long total4 = M * N / 4;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)ceil_div64(total4, 256)), dim3(256), 0, st,
-                       part, out, bias, (const float*)nullptr, total4, N, splits, relu, 0, (float*)nullptr);
-}
-
 // Which tile / split-K factor / K tile phnet_conv2d_fwd runs a GEMM of M x Co x K with (a 1x1 convolution of K channels over M
 // pixels; M < 2^31).  Answered by the pick_conv the launch itself calls.
 PHNET_API int phnet_conv2d_plan(int64_t M, int32_t Co, int32_t K, uint64_t ws_bytes, int32_t* bm, int32_t* bn, int32_t* splits,
@@ -503,8 +495,8 @@ PHNET_API int phnet_conv2d_plan(int64_t M, int32_t Co, int32_t K, uint64_t ws_by
     ConvShape g;
     if (M < 1 || M > 0x7fffffffL || Co < 1 || K < 1 || !bm || !bn || !splits || !k_tile) return PHNET_ERR_ARG;
     fwd_shape((int)M, 1, 1, K, Co, 1, 1, 1, 0, &g);
-    const ConvPick p = pick_conv(g, false, ws_bytes > 0, (size_t)ws_bytes);
-    *bm = p.bm; *bn = p.bn; *splits = p.splits; *k_tile = p.bkt;
+    const ConvPick p = pick_conv(g, false, ws_bytes > 0, (size_t)ws_bytes, false);
+    *bm = p.bm; *bn = p.bn; *splits = p.splits; *k_tile = p.rows ? BK : p.bkt;
     return PHNET_OK;
 }
 
@@ -517,7 +509,7 @@ PHNET_API int phnet_conv2d_kernel(int32_t dgrad, int32_t N, int32_t Hi, int32_t 
     if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad) || N < 1 || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
     if (dgrad ? (stride > 2 || !dgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) : !fwd_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g))
         return PHNET_ERR_ARG;
-    const ConvPick p = pick_conv(g, dgrad != 0, ws_bytes > 0, (size_t)ws_bytes);
+    const ConvPick p = pick_conv(g, dgrad != 0, ws_bytes > 0, (size_t)ws_bytes, false);
     *splits = p.splits;
     return conv_kernel_name(p, name, name_cap);
 }

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(THREADS) void conv_igemm_kernel(
 // What one forward / data-gradient call launches.  Decided once (pick_conv); launch_conv launches it, conv_kernel_name spells it.
 struct ConvPick {
     bool taps3;                          // conv3x3s1_kernel<dgrad>; else conv_igemm_kernel<bm, bn, dgrad, bkt, uni, mma, pf, buf>
+    int rows;                            // 1 | 2: linrows_kernel<dgrad, rows> (linrows.hip) on bm x bn = 160 * rows x 128 tiles of 16-deep steps;
+                                         // bkt is still the K tile whose multiples the splits take, as in the generic kernel
     bool dgrad, uni, buf;
     int bm, bn, bkt, mma, pf, splits;
     long tiles;

@@ -1,13 +1,18 @@
-// Internal (not part of the C-ABI): what csrc/linrows.hip takes from csrc/conv.hip, so that the split of a reduction and the reduce
-// launch are stated once.
+// Internal (not part of the C-ABI): what csrc/conv.hip takes from csrc/linrows.hip.  pick_conv asks linrows_wm once it has the plan,
+// launch_conv launches through linrows_launch (the split of K and the reduce launch stay conv.hip's own), conv_kernel_name spells
+// LINROWS_NAME.
 #pragma once
 #include "common.h"
 
-struct ConvSplit { int splits, k_per_split; };
+// linrows_kernel<dgrad, wm>, as rocprofv3 spells it: printf format of ("false" | "true", wm)
+constexpr const char* LINROWS_NAME = "linrows_kernel<%s, %d>";
 
-// Split-K factor and K range per split that phnet_conv2d_fwd (dgrad = false: x [M][K], w [N][K]) or phnet_conv2d_dgrad (dgrad = true:
-// dy [M][K], w [K][N]) runs the Linear layer M x N, reduction depth K, with - pick_conv's answer for the current tuning state.
-ConvSplit phnet_linear_split(long M, int K, int N, bool dgrad, bool has_ws, size_t ws_bytes);
+// The WM (1: 160-row tiles, 2: 320-row tiles) of the linrows_kernel<DGRAD, WM> that takes the Linear layer of M rows, N columns and
+// reduction depth K which the plan cuts into `splits` - or 0: it stays on the generic kernel.  Reads tuning().linrows (0: never,
+// 1: the shape class measured faster, 2: whatever the kernel can run).
+int linrows_wm(long M, int K, int N, int splits);
 
-// out [M][N] = sum of the `splits` slabs of `part` (+ bias) (ReLU): the splitk_reduce_kernel launch of launch_conv
-void phnet_splitk_reduce(const float* part, float* out, const float* bias, long M, int N, int splits, int relu, hipStream_t st);
+// The GEMM launch alone: dst [splits][M][N] (the output itself where splits == 1, with bias and ReLU; else the raw partial sums) from
+// a [M][K] and w ([N][K] forward, [K][N] data gradient).  k_per_split: a multiple of 16.  false: the launch could not be set up.
+bool linrows_launch(bool dgrad, int wm, const float* a, const float* w, const float* bias, float* dst, long M, int K, int N, int splits,
+                    int k_per_split, int relu, hipStream_t st);

@@ -12,8 +12,8 @@
 // The results are the generic kernel's bit for bit: an output element's bits depend only on its accumulation chain, and that is the
 // chain of igemm_tile - v_mfma_f32_32x32x16_bf16 on 16-deep sub-steps in ascending K from the split's k_begin, lane (r, h) holding
 // k = 8h .. 8h+7, the six terms in mma3_step's order, accumulators seeded with the bias (unsplit) or zeros (split), and the split
-// of K and the reduce launch are conv.hip's own (linrows.h).
-#include <cstdio>
+// of K and the reduce launch are conv.hip's own: pick_conv decides for this kernel, launch_conv launches it (linrows.h) and the
+// generic entry points phnet_conv2d_fwd / _fwd_fused / _dgrad are the only way in.
 #include <type_traits>
 #include "conv_common.h"
 #include "linrows.h"
@@ -190,39 +190,6 @@ bool rows_ok(long M, int K, int N)
            (M + 320) * K * 4 < 0x7fffffffL && (long)N * K * 4 < 0x7fffffffL && (M + 320) * N * 4 < 0x7fffffffL;
 }
 
-struct RowsPlan { int wm, splits, k_per_split; long tiles_m, tiles_n; };
-
-RowsPlan rows_plan(long M, int K, int N, bool dgrad, size_t ws_bytes)
-{
-    const ConvSplit s = phnet_linear_split(M, K, N, dgrad, ws_bytes > 0, ws_bytes);
-    RowsPlan p;
-    p.splits = s.splits;
-    p.k_per_split = s.k_per_split;
-    p.wm = s.splits == 1 ? 2 : 1;                           // 320 rows unsplit, 160 where split-K multiplies the workgroups
-    p.tiles_m = cdiv(M, p.wm * R_FM * 32);
-    p.tiles_n = cdiv(N, R_TN);
-    return p;
-}
-
-// The shapes this kernel was measured faster at than the generic one: many-row layers - never the few-rows ones,
-// which have kernels of their own - with whole column tiles, a deep reduction, and a plan that is one (nearly) full round of the CUs.
-bool rows_applies(long M, int K, int N, bool dgrad)
-{
-    const Tuning& tn = tuning();
-    if (!tn.linrows || tn.force_bm || tn.force_kt || !rows_ok(M, K, N)) return false;
-    if (M <= 256 || M > 2048 || (N % R_TN) != 0 || K < 1024) return false;
-    // the split-K workspace hip_ops.conv2d_fwd / conv2d_dgrad hand a launch with M x N outputs
-    const size_t ws_bytes = M * N < (1L << 23) ? (size_t)8 * M * N * 4 : 0;
-    const RowsPlan p = rows_plan(M, K, N, dgrad, ws_bytes);
-    const long wgs = p.tiles_m * p.tiles_n * p.splits;
-    return wgs > R_CUS * 3 / 4 && wgs <= R_CUS;
-}
-
-int rows_kernel_name(const RowsPlan& p, bool dgrad, char* name, int cap)
-{
-    return snprintf(name, (size_t)cap, "linrows_kernel<%s, %d>", dgrad ? "true" : "false", p.wm) < cap ? PHNET_OK : PHNET_ERR_ARG;
-}
-
 template <bool DGRAD, int WM>
 bool launch_rows_as(const float* a, const float* w, const float* bias, float* dst, const RowsShape& g, int relu, dim3 grid, hipStream_t st)
 {
@@ -233,53 +200,29 @@ bool launch_rows_as(const float* a, const float* w, const float* bias, float* ds
     return true;
 }
 
-template <bool DGRAD>
-int launch_rows(const float* a, const float* w, const float* bias, float* out, long M, int K, int N, int relu, float* workspace,
-                size_t ws_bytes, hipStream_t st)
-{
-    const RowsPlan p = rows_plan(M, K, N, DGRAD, workspace ? ws_bytes : 0);
-    const RowsShape g{(int)M, K, N, p.splits, p.k_per_split, (int)p.tiles_m};
-    float* dst = p.splits > 1 ? workspace : out;
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.splits);
-    if (!(p.wm == 2 ? launch_rows_as<DGRAD, 2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_as<DGRAD, 1>(a, w, bias, dst, g, relu, grid, st)))
-        return PHNET_ERR_LAUNCH;
-    if (p.splits > 1) phnet_splitk_reduce(workspace, out, bias, M, N, p.splits, relu, st);
-    return phnet_launch_status();
-}
-
 }  // namespace
 
-// ---- C-ABI ---------------------------------------------------------------------------------------------------------
-// Does hip_ops.linear_fwd (dgrad = 0: x [M][K], w [N][K]) / linear_dgrad (dgrad = 1: dy [M][K], w [K][N]) run this kernel for the shape?
-PHNET_API int phnet_linrows_applies(int64_t M, int32_t K, int32_t N, int32_t dgrad)
+// ---- what csrc/conv.hip takes from here (linrows.h) --------------------------------------------------------------------------------
+// Mode 1, the shapes this kernel was measured faster at than the generic one: many-row layers - never the
+// few-rows ones, which have kernels of their own - with whole column tiles, a deep reduction, a plan nobody forced, and a launch that
+// is one (nearly) full round of the CUs.
+int linrows_wm(long M, int K, int N, int splits)
 {
-    return rows_applies((long)M, K, N, dgrad != 0) ? 1 : 0;
+    const Tuning& tn = tuning();
+    if (!tn.linrows || !rows_ok(M, K, N)) return 0;
+    const int wm = splits == 1 ? 2 : 1;                     // 320 rows unsplit, 160 where split-K multiplies the workgroups
+    if (tn.linrows == 2) return wm;
+    if (tn.force_bm || tn.force_kt || M <= 256 || M > 2048 || (N % R_TN) != 0 || K < 1024) return 0;
+    const long wgs = cdiv(M, wm * R_FM * 32) * cdiv(N, R_TN) * splits;
+    return wgs > R_CUS * 3 / 4 && wgs <= R_CUS ? wm : 0;
 }
 
-// Host-only query: the instantiation phnet_linrows_fwd / _dgrad launches for this shape (as rocprofv3 spells it) and its split-K factor
-PHNET_API int phnet_linrows_kernel(int64_t M, int32_t K, int32_t N, int32_t dgrad, uint64_t ws_bytes, char* name, int32_t name_cap,
-                                   int32_t* splits)
+bool linrows_launch(bool dgrad, int wm, const float* a, const float* w, const float* bias, float* dst, long M, int K, int N, int splits,
+                    int k_per_split, int relu, hipStream_t st)
 {
-    if (!rows_ok((long)M, K, N) || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
-    const RowsPlan p = rows_plan((long)M, K, N, dgrad != 0, (size_t)ws_bytes);
-    *splits = p.splits;
-    return rows_kernel_name(p, dgrad != 0, name, name_cap);
-}
-
-// y [M][N] = x [M][K] * w [N][K]^T (+ bias) (ReLU): phnet_conv2d_fwd's result on the [M][1][1][K] image, bit for bit
-PHNET_API int phnet_linrows_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t K, int32_t N,
-                                int32_t relu, void* workspace, uint64_t ws_bytes, void* stream)
-{
-    if (M == 0) return PHNET_OK;
-    if (!x || !w || !y || !rows_ok((long)M, K, N)) return PHNET_ERR_ARG;
-    return launch_rows<false>(x, w, bias, y, (long)M, K, N, relu, (float*)workspace, (size_t)ws_bytes, (hipStream_t)stream);
-}
-
-// dx [M][N] = dy [M][K] * w [K][N] (w as the forward uses it: [out features = K][in features = N]): phnet_conv2d_dgrad's result
-PHNET_API int phnet_linrows_dgrad(const float* dy, const float* w, float* dx, int64_t M, int32_t K, int32_t N, void* workspace,
-                                  uint64_t ws_bytes, void* stream)
-{
-    if (M == 0) return PHNET_OK;
-    if (!dy || !w || !dx || !rows_ok((long)M, K, N)) return PHNET_ERR_ARG;
-    return launch_rows<true>(dy, w, nullptr, dx, (long)M, K, N, 0, (float*)workspace, (size_t)ws_bytes, (hipStream_t)stream);
+    const long tiles_m = cdiv(M, wm * R_FM * 32);
+    const RowsShape g{(int)M, K, N, splits, k_per_split, (int)tiles_m};
+    const dim3 grid((unsigned)(tiles_m * cdiv(N, R_TN)), 1, (unsigned)splits);
+    if (dgrad) return wm == 2 ? launch_rows_as<true, 2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_as<true, 1>(a, w, bias, dst, g, relu, grid, st);
+    return wm == 2 ? launch_rows_as<false, 2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_as<false, 1>(a, w, bias, dst, g, relu, grid, st);
 }

@@ -10,7 +10,8 @@ struct Tuning {
     int buf_loads = 1;           // buffer-load operand path where it applies (phnet_tune_force_k_tile(-200 / -201))
     int uniform_tap = 1;         // uniform-tap kernel variant (phnet_tune_force_k_tile(-1 / -2) = off / on)
     int taps3 = 1;               // three-taps 3x3 / stride-1 forward / dgrad kernel (phnet_tune_force_k_tile(-5 / -6) = off / on)
-    int linrows = 1;             // tall-tile producer / consumer kernel for the many-row Linear layers (linrows.hip; phnet_tune_force_k_tile(-300 / -301) = off / on)
+    int linrows = 1;             // tall-tile producer / consumer kernel for the many-row Linear layers (linrows.hip; phnet_tune_force_k_tile(-300 / -301) = off / on;
+                                 // -302 = 2: for EVERY Linear launch without addend / statistics the kernel can run, whatever its size and the forced plan)
     int deep_kt3 = 64;           // K tile of the few-rows GEMMs in mode 3 (phnet_tune_force_k_tile(-32 / -64))
     // ---- forced forward / dgrad plan (0 = heuristic) ----
     int force_bm = 0, force_bn = 0, force_splits = 0;       // phnet_tune_force_conv_tile

@@ -24,7 +24,7 @@ PHNET_API int phnet_tune_force_k_tile(int32_t kt)
     if (kt == -32 || kt == -64) { t.deep_kt3 = -kt; return PHNET_OK; }
     if (kt == -101 || kt == -102 || kt == -104) { t.pf = -kt - 100; return PHNET_OK; }
     if (kt == -200 || kt == -201) { t.buf_loads = -kt - 200; return PHNET_OK; }
-    if (kt == -300 || kt == -301) { t.linrows = -kt - 300; return PHNET_OK; }
+    if (kt <= -300 && kt >= -302) { t.linrows = -kt - 300; return PHNET_OK; }
     if (kt != 0 && kt != 16 && kt != 32 && kt != 64) return PHNET_ERR_ARG;
     t.force_kt = kt;
     return PHNET_OK;

@@ -132,6 +132,13 @@ def conv_out_hw(hi, wi, r, s, stride, pad):
     return (hi + 2 * pad - r) // stride + 1, (wi + 2 * pad - s) // stride + 1
 
 
+def splitk_workspace_bytes(m: int, cols: int) -> int:
+    """Split-K scratch every forward / data-gradient launch with an [m, cols] output is handed: room for 8 slabs of partial sums.
+    The plan (csrc/conv.hip plan_conv) sees the size THIS shape asks for, not whatever the shared buffer has grown to - the same
+    shape always runs the same plan, whatever ran before it in the process."""
+    return 8 * m * cols * 4 if m * cols < (1 << 23) else 0
+
+
 def conv2d_fwd(x, w, bias, stride: int, pad: int, relu: bool = False, out: Optional[torch.Tensor] = None,
                addend: Optional[torch.Tensor] = None, stats: bool = False):
     """x NHWC [N,Hi,Wi,Ci]; w OHWI [Co,R,S,Ci]; -> NHWC [N,Ho,Wo,Co].
@@ -145,29 +152,26 @@ def conv2d_fwd(x, w, bias, stride: int, pad: int, relu: bool = False, out: Optio
     ho, wo = conv_out_hw(hi, wi, r, s, stride, pad)
     if out is None:
         out = torch.empty((n, ho, wo, co), dtype=torch.float32, device=x.device)
-    # split-K scratch: the plan (csrc/conv.hip plan_conv) sees the size THIS shape asks for, not whatever the shared buffer
-    # has grown to - the same shape always runs the same plan, whatever ran before it in the process
-    need = 8 * n * ho * wo * co * 4 if n * ho * wo * co < (1 << 23) else 0
-    ws = workspace(need, x.device) if need else None
     m, k = n * ho * wo, r * s * ci
+    need = splitk_workspace_bytes(m, co)
+    ws = workspace(need, x.device) if need else None
+    part, nblk = None, 0
+    if stats:
+        nblk = int(lib().phnet_conv2d_stats_blocks(m, co, k, need))
+        part = workspace(nblk * 2 * co * 4, x.device, 1)
+    if addend is not None:
+        _req(addend, name="addend")
+        assert addend.shape == out.shape
     if addend is not None or stats:
-        part, nblk = None, 0
-        if stats:
-            nblk = int(lib().phnet_conv2d_stats_blocks(m, co, k, need))
-            part = workspace(nblk * 2 * co * 4, x.device, 1)
-        if addend is not None:
-            _req(addend, name="addend")
-            assert addend.shape == out.shape
-        _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 0, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * m * co * k,
-                      lambda: check(lib().phnet_conv2d_fwd_fused(_ptr(x), _ptr(w), _ptr(bias), _ptr(addend), _ptr(out), _ptr(part), n, hi, wi,
-                                                                 ci, co, r, s, stride, pad, int(relu), _ptr(ws), need, _stream()),
-                                    "phnet_conv2d_fwd_fused"), shape=("fwd", m, co, k, r), nbytes=4.0 * (n * hi * wi * ci + m * co + co * k))
-        return (out, (part, nblk)) if stats else out
-    _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 0, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * m * co * k,
-                  lambda: check(lib().phnet_conv2d_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), n, hi, wi, ci, co, r, s, stride,
-                                                       pad, int(relu), _ptr(ws), need, _stream()), "phnet_conv2d_fwd"),
+        launch = lambda: check(lib().phnet_conv2d_fwd_fused(_ptr(x), _ptr(w), _ptr(bias), _ptr(addend), _ptr(out), _ptr(part), n, hi, wi,
+                                                            ci, co, r, s, stride, pad, int(relu), _ptr(ws), need, _stream()),
+                               "phnet_conv2d_fwd_fused")
+    else:
+        launch = lambda: check(lib().phnet_conv2d_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), n, hi, wi, ci, co, r, s, stride,
+                                                      pad, int(relu), _ptr(ws), need, _stream()), "phnet_conv2d_fwd")
+    _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 0, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * m * co * k, launch,
                   shape=("fwd", m, co, k, r), nbytes=4.0 * (n * hi * wi * ci + m * co + co * k))
-    return out
+    return (out, (part, nblk)) if stats else out
 
 
 def conv3p_applies(m: int, ca: int, nn: int) -> bool:
@@ -231,7 +235,7 @@ def conv3p(x: torch.Tensor, packed: torch.Tensor, nn: int, dgrad: bool = False, 
     n, h, w_, ca = x.shape
     out = torch.empty((n, h, w_, nn), dtype=torch.float32, device=x.device)
     m = n * h * w_
-    need = 8 * m * nn * 4 if m * nn < (1 << 23) else 0
+    need = splitk_workspace_bytes(m, nn)
     ws = workspace(need, x.device) if need else None
     part, nblk = None, 0
     if stats:
@@ -257,9 +261,9 @@ def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: O
     hi, wi = in_hw
     dx = torch.empty((n, hi, wi, ci), dtype=torch.float32, device=dy.device) if out is None else _req(out, name="out")
     assert dx.shape == (n, hi, wi, ci)
-    need = 8 * n * hi * wi * ci * 4 if n * hi * wi * ci < (1 << 23) else 0
-    ws = workspace(need, dy.device) if need else None
     m, k = n * hi * wi, r * s * co
+    need = splitk_workspace_bytes(m, ci)
+    ws = workspace(need, dy.device) if need else None
     _timed_launch(lambda: _kernel(lib().phnet_conv2d_kernel, 1, n, hi, wi, ci, co, r, s, stride, pad, need), 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * co * r * s * ci,
                   lambda: check(lib().phnet_conv2d_dgrad(_ptr(dy), _ptr(w), _ptr(addend), _ptr(dx), n, hi, wi, ci, co, r, s, stride,
                                                          pad, _ptr(ws), need, _stream()), "phnet_conv2d_dgrad"),
@@ -291,43 +295,15 @@ def conv2d_wgrad(dy, x, w_shape, stride: int, pad: int, dw: Optional[torch.Tenso
     return dw
 
 
-def linrows_applies(m: int, k: int, n: int, dgrad: bool) -> bool:
-    """Does the tall-tile kernel of csrc/linrows.hip take this Linear layer?  (m rows, reduction depth k, n output columns)"""
-    return bool(lib().phnet_linrows_applies(int(m), int(k), int(n), int(dgrad)))
-
-
-def _linrows(dgrad: bool, a2d, w, bias, relu: bool, n: int):
-    """a2d [M,K] -> [M,n] on csrc/linrows.hip: the generic kernel's result bit for bit, with the split-K scratch conv2d_fwd /
-    conv2d_dgrad would hand the same output."""
-    _req(a2d, name="x"); _req(w, name="w")
-    m, k = a2d.shape
-    out = torch.empty((m, n), dtype=torch.float32, device=a2d.device)
-    need = 8 * m * n * 4 if m * n < (1 << 23) else 0
-    ws = workspace(need, a2d.device) if need else None
-    if dgrad:
-        launch = lambda: check(lib().phnet_linrows_dgrad(_ptr(a2d), _ptr(w), _ptr(out), m, k, n, _ptr(ws), need, _stream()),
-                               "phnet_linrows_dgrad")
-    else:
-        launch = lambda: check(lib().phnet_linrows_fwd(_ptr(a2d), _ptr(w), _ptr(bias), _ptr(out), m, k, n, int(relu), _ptr(ws), need,
-                                                       _stream()), "phnet_linrows_fwd")
-    _timed_launch(lambda: _kernel(lib().phnet_linrows_kernel, m, k, n, int(dgrad), need), 2.0 * m * n * k, launch,
-                  shape=("dgrad" if dgrad else "fwd", m, n, k, 1), nbytes=4.0 * (m * k + m * n + n * k))
-    return out
-
-
 def linear_fwd(x2d, w, bias, relu: bool = False):
     """x [M,K], w [N,K] -> [M,N] (= conv 1x1 on an [M,1,1,K] image)."""
     m, k = x2d.shape
-    if linrows_applies(m, k, w.shape[0], False):
-        return _linrows(False, x2d, w, bias, relu, w.shape[0])
     return conv2d_fwd(x2d.view(m, 1, 1, k), w.view(w.shape[0], 1, 1, k), bias, 1, 0, relu).view(m, w.shape[0])
 
 
 def linear_dgrad(dy2d, w):
     m, n = dy2d.shape
     k = w.shape[1]
-    if linrows_applies(m, n, k, True):
-        return _linrows(True, dy2d, w, None, False, k)
     return conv2d_dgrad(dy2d.view(m, 1, 1, n), w.view(n, 1, 1, k), (1, 1), 1, 0).view(m, k)
 
 
@@ -1756,7 +1732,8 @@ def mask_metric_counts(pred, gt, radius: int, out=None):
 
 def tune_k_tile(code: int) -> None:
     """Benchmark aid (process-global): phnet_tune_force_k_tile; -5 / -6 switch the three-taps 3x3 forward / dgrad kernel off / on,
-    -300 / -301 the tall-tile kernel of the many-row Linear layers (csrc/linrows.hip)."""
+    -300 / -301 the tall-tile kernel of the many-row Linear layers (csrc/linrows.hip), -302 takes it for every Linear launch
+    without addend / statistics that it can run, whatever the size or the forced plan."""
     check(lib().phnet_tune_force_k_tile(code), "phnet_tune_force_k_tile")
 
 

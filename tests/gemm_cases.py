@@ -11,6 +11,8 @@ A row is (op, shape, kernel, splits, reason):
 No torch.cuda here: the module only describes shapes and restates the launch arithmetic."""
 import collections
 
+from phnet_amd.hip_ops import splitk_workspace_bytes      # the scratch hip_ops hands a launch with an [m, cols] output (importing it touches no GPU)
+
 Row = collections.namedtuple("Row", "op shape kernel splits reason")
 
 IGEMM = "conv_igemm_kernel<%s>"
@@ -25,6 +27,8 @@ P3_1, P3_2 = "conv3p_kernel<1>", "conv3p_kernel<2>"
 W3S, W3, W1S = "wgrad3s_kernel<2>", "conv_wgrad3x3_kernel<4, 16>", "wgrad1s_kernel"
 WG64, WG128 = "conv_wgrad_kernel<64, 64, 3, 16, 4, true>", "conv_wgrad_kernel<128, 64, 3, 16, 4, true>"
 SMALLP = "linear_wgrad_smallp_kernel<64, 64, 0>"
+ROWS1, ROWS2 = "linrows_kernel<false, 1>", "linrows_kernel<false, 2>"                # 160 | 320 x 128 tiles, 16-deep steps
+ROWS1_D, ROWS2_D = "linrows_kernel<true, 1>", "linrows_kernel<true, 2>"
 
 ROWS = [
     # ---- 128-row tiles (the 8-clip trunk plans), unsplit: ragged rows and columns, stride-2 data gradient
@@ -53,16 +57,22 @@ ROWS = [
     Row("fwd", (1, 20, 50, 80, 80, 3, 1, 1), TAPS3, 2, "short_split"),              # 15 units: 8 + 7
     Row("dgrad", (1, 20, 50, 80, 80, 3, 1, 1), TAPS3_D, 2, "short_split"),
     # ---- the production 64x64 tile at every split count the fixture records
-    Row("fwd", (1200, 1, 1, 4608, 1024, 1, 1, 0), T64, 4, "split4"),
+    Row("fwd", (1200, 1, 1, 4608, 1040, 1, 1, 0), T64, 4, "split4"),                # 1040 columns: no whole 128-column tiles, so not ROWS1
     Row("fwd", (613, 1, 1, 784, 2556, 1, 1, 0), T64, 3, "odd_split"),
     Row("fwd", (613, 1, 1, 1296, 1600, 1, 1, 0), T64, 5, "odd_split"),
     Row("fwd", (763, 1, 1, 1792, 960, 1, 1, 0), T64, 7, "odd_split"),
     Row("fwd", (320, 1, 1, 2064, 64, 1, 1, 0), T64, 8, "short_split"),              # 129 K steps: 7 x 17 + 10
     Row("dgrad", (613, 1, 1, 3836, 528, 1, 1, 0), T64_D, 2, "short_split"),
     Row("dgrad", (613, 1, 1, 2556, 784, 1, 1, 0), T64_D, 3, "odd_split"),
-    Row("dgrad", (613, 1, 1, 1920, 1040, 1, 1, 0), T64_D, 4, "short_split"),
+    Row("dgrad", (613, 1, 1, 1924, 1040, 1, 1, 0), T64_D, 4, "short_split"),        # 65 K steps: 17 17 17 14; 1924 columns: not ROWS1_D
     Row("dgrad", (320, 1, 1, 64, 2064, 1, 1, 0), T64_D, 8, "short_split"),
     Row("dgrad", (3, 40, 40, 512, 64, 3, 2, 1), T64_D_DILATED, 2, "dilated_split"),
+    # ---- tall tiles for many-row Linear layers: the smallest shapes of the class (more than 192 workgroups of 160 x 128 outputs)
+    Row("fwd", (321, 1, 1, 1024, 2176, 1, 1, 0), ROWS1, 4, "split4"),               # 3 x 17 tiles x 4 splits = 204 workgroups
+    Row("dgrad", (321, 1, 1, 2176, 1024, 1, 1, 0), ROWS1_D, 4, "split4"),
+    Row("fwd", (321, 1, 1, 1792, 1280, 1, 1, 0), ROWS1, 7, "odd_split"),            # 3 x 10 x 7 = 210 (the fixture's 8-clip 2304 -> 384 plan)
+    Row("fwd", (321, 1, 1, 1024, 12416, 1, 1, 0), ROWS2, 1, "unsplit"),             # 2 x 97 tiles = 194 workgroups, ragged rows
+    Row("dgrad", (321, 1, 1, 12416, 1024, 1, 1, 0), ROWS2_D, 1, "unsplit"),
     # ---- packed-weight 3x3: the unsplit plans and the 128-column tile (the existing list reaches conv3p_kernel<1> at 3, 6, 8)
     Row("conv3p_fwd", (2, 16, 20, 16, 64), P3_1, 1, "unsplit"),
     Row("conv3p_dgrad", (2, 16, 20, 64, 16), P3_1, 1, "unsplit"),
@@ -98,11 +108,6 @@ def row_id(row: Row) -> str:
 
 def conv_out_hw(hi, wi, r, stride, pad):
     return (hi + 2 * pad - r) // stride + 1, (wi + 2 * pad - r) // stride + 1
-
-
-def splitk_workspace_bytes(m: int, cols: int) -> int:
-    """Split-K scratch hip_ops.conv2d_fwd / conv2d_dgrad / conv3p hand the launch for an [m, cols] output."""
-    return 8 * m * cols * 4 if m * cols < (1 << 23) else 0
 
 
 def query_args(lib, op: str, shape) -> dict:
@@ -148,7 +153,7 @@ def reduction_steps(row: Row):
         a_channels = ci if row.op == "fwd" else co
         if row.kernel in (TAPS3, TAPS3_D):
             return 3 * (a_channels // 16)
-        k_tile = int(row.kernel.split(",")[3])
+        k_tile = 16 if row.kernel.startswith("linrows_kernel<") else int(row.kernel.split(",")[3])
         return -(-(r * r * a_channels) // k_tile)
     ho, wo = conv_out_hw(hi, wi, r, stride, pad)
     return -(-(n * ho * wo) // WGRAD_PIXELS_PER_STEP[row.kernel])

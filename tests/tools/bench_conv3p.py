@@ -54,7 +54,7 @@ def main():
         t_pack = timeit(lambda: K.conv3p_pack(wt, False, pf))
         gf = 2.0 * n * h * w * co * 9 * ci / 1e9
         m = n * h * w
-        need = 8 * m * co * 4 if m * co < (1 << 23) else 0
+        need = K.splitk_workspace_bytes(m, co)
         print(f"{name:8s} M={m:6d} C={ci:3d}: err vs fp64 new {e_new:.2e} old {e_old:.2e} | dgrad vs old {ed:.2e} | fused {ef:.2e} | stats {es:.1e} {eq:.1e} | "
               f"fwd old {t_old:6.1f} us ({gf / t_old * 1e3:5.1f} TF/s) new {t_new:6.1f} us ({gf / t_new * 1e3:5.1f} TF/s) splits {K._kernel(lib().phnet_conv3p_kernel, m, ci, co, need)[1]} | "
               f"dgrad old {t_oldd:6.1f} new {t_newd:6.1f} us | pack {t_pack:5.1f} us", flush=True)

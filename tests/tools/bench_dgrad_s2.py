@@ -75,7 +75,7 @@ def main():
         ho, wo = K.conv_out_hw(hi, wi, r, r, stride, pad)
         dy = torch.randn(n, ho, wo, co, device="cuda")
         w = torch.randn(co, r, r, ci, device="cuda") * (ci * r * r) ** -0.5
-        need = 8 * n * hi * wi * ci * 4 if n * hi * wi * ci < (1 << 23) else 0
+        need = K.splitk_workspace_bytes(n * hi * wi, ci)
         ws = K.workspace(need, dy.device) if need else None
         kernel, splits = K._kernel(libs["branch"].phnet_conv2d_kernel, 1, n, hi, wi, ci, co, r, r, stride, pad, need)
         dx = {k: torch.full((n, hi, wi, ci), float("nan"), device="cuda") for k in libs}
