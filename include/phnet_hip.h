@@ -241,6 +241,13 @@ int phnet_conv3p_pack(const float* w, void* packed, int32_t Co, int32_t Ci, int3
 /* all 3x3 weights of a model in one launch: jobs = DEVICE array of njobs records {const float* w; void* dst; int32 Co, Ci, dgrad, 0;
  * int64 first} sorted by `first` = running sum of the jobs' item counts 9*(Ca/16)*(Nn/32)*64; total = the sum of all counts */
 int phnet_conv3p_pack_jobs(const void* jobs, int32_t njobs, int64_t total, void* stream);
+/* The one-plane image of the bf16 inference arithmetic (phnet_tune_mma(4), include/phnet_hip_tuning.h): every weight rounded to
+ * bf16 once, same fragment order, exactly a third of phnet_conv3p_packed_bytes; forward packing only (job records with dgrad = 0).
+ * While mode 4 is set, phnet_conv3p_fwd takes THIS image (and the three-plane one in every other mode): the caller keeps the
+ * image and the mode of the launch together. */
+uint64_t phnet_conv3p_packed_bytes_bf16(int32_t Co, int32_t Ci);
+int phnet_conv3p_pack_bf16(const float* w, void* packed, int32_t Co, int32_t Ci, void* stream);
+int phnet_conv3p_pack_jobs_bf16(const void* jobs, int32_t njobs, int64_t total, void* stream);
 uint64_t phnet_conv3p_stats_blocks(int64_t M, int32_t Ca, int32_t Nn, uint64_t ws_bytes);
 int phnet_conv3p_fwd(const float* x, const void* packed, const float* bias, const float* addend, float* y, float* stats,
                      int32_t N, int32_t H, int32_t W, int32_t Ca, int32_t Nn, int32_t relu,

@@ -19,7 +19,8 @@ int phnet_tune_force_k_tile(int32_t k_tile);   /* 0 = heuristic, else 16 | 32 | 
                                                   on for the shape class it was measured faster at; -302: on for every Linear-shaped
                                                   phnet_conv2d_fwd / _dgrad launch without addend / statistics that it can run (arithmetic
                                                   mode 3, K % 16 == 0, operands below 2 GB), whatever the rows, columns, depth, forced tile
-                                                  or forced K tile - how tests reach it at small shapes */
+                                                  or forced K tile - how tests reach it at small shapes;
+                                                  -400 / -401: arithmetic mode 4 without (default) / with mode 3's split-K plan */
 int phnet_tune_wgrad(int32_t allow_bm128, int32_t target_blocks);   /* wgrad tile / split-K policy; bits of the first argument:
                                                                         1 = no few-rows Linear kernel, 3 = no three-taps 3x3 kernel,
                                                                         4 = its 32-pixel steps, 5 = no producer / consumer variant
@@ -27,7 +28,25 @@ int phnet_tune_wgrad(int32_t allow_bm128, int32_t target_blocks);   /* wgrad til
                                                                         kernel (csrc/wgrad1s.hip); a NEGATIVE second argument sets the
                                                                         three-taps kernel's workgroup target (default 256) */
 /* arithmetic of the GEMM kernels: 3 = exact three-term bf16 split staged in LDS (library default), 0 = f32-input MFMA,
- * 1 = two-term bf16 split in registers (3 MFMAs per product, ~2^-16 per product), 2 = three-term split in registers */
+ * 1 = two-term bf16 split in registers (3 MFMAs per product, ~2^-16 per product), 2 = three-term split in registers,
+ * 4 = bf16 inference arithmetic (Python name "bf16").  The rule of mode 4:
+ *   - a forward GEMM rounds every element of both operands to bf16, round to nearest even, exactly once, while the tile is staged
+ *     (weights of the packed 3x3 kernel: while they are packed).  The operands are the f32 activations the launch was given and the
+ *     f32 weights the fp32 path would have used (after the eval-mode BatchNorm fold); the conversion is the one the exact split
+ *     uses for its `hi` term;
+ *   - products are exact in f32 (8 + 8 mantissa bits) and are summed in the f32 accumulators of v_mfma_f32_32x32x16_bf16, ONE MFMA
+ *     per 16-deep product (mode 3: six);
+ *   - bias, addend (residual), ReLU, split-K partial sums and the statistics rows stay f32, exactly as in mode 3; outputs are f32;
+ *   - forward only: phnet_conv2d_dgrad, phnet_conv2d_wgrad, phnet_linear_bwd and the backward queries (phnet_conv2d_kernel with
+ *     dgrad = 1, phnet_conv2d_wgrad_kernel, phnet_linear_bwd_kernel) return PHNET_ERR_ARG; phnet_conv3p_fwd takes the one-plane image
+ *     of phnet_conv3p_pack_bf16, which has no data-gradient packing;
+ *   - no forward launch runs silently in another arithmetic: every forward kernel a shape can be dispatched to in mode 4 is a
+ *     mode-4 instantiation (conv_igemm_kernel<..., 4, ...>, conv3p_bf16_kernel, linrows_bf16_kernel); the three-taps kernel, which has
+ *     none, is not selected.
+ *   - mode 4 does not split K on its own (a forced split count is honoured; phnet_tune_force_k_tile(-401) gives it mode 3's split
+ *     plan back): unsplit, an output's bits do not depend on the batch it was computed in, so a stream step equals the clip.
+ * Kernels that do not read the mode (dynamic head, row chains, towers, attention, gate) keep their arithmetic.
+ * Modes 3 and 4 run with a 4-tile register ring (pf), the others with 1. */
 int phnet_tune_mma(int32_t mode);
 /* packed-weight 3x3 kernel: workgroups a launch is topped up to by split-K (default 512); -1 / -2: 128-column tiles off / on */
 int phnet_conv3p_tune(int32_t target_workgroups);

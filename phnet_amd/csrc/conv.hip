@@ -324,6 +324,11 @@ __global__ void pad_channels_kernel(const float* __restrict__ src, float* __rest
 
 struct TileChoice { int bm, bn; };
 
+// Modes 3 and 4 stage bf16 planes (three / one per operand).  The plan of mode 4 - tile, K-tile depth, ring depth - is mode 3's,
+// decision for decision: at one clip these loops are bound by operand latency, which the arithmetic does not change.  The split count
+// is not: plan_conv (profiles/README.md "bf16 inference" has what was measured).
+inline bool staged(int mma) { return mma == 3 || mma == 4; }
+
 TileChoice pick_tile(long M, long N)
 {
     // Measured on MI355X (tests/tools/bench_conv.py): the problems of this path are small (a 5-frame clip), so what
@@ -332,7 +337,7 @@ TileChoice pick_tile(long M, long N)
     const int mma = tuning().mma_mode;
     // (64x64 is the fastest tile of THIS kernel up to the 1200 rows of a batched clip; the Linear layers of that size whose launch
     // fits one round of tall tiles keep this plan's split count and leave for linrows.hip in pick_conv)
-    if (mma == 3 && M <= 2048) return {64, 64};
+    if (staged(mma) && M <= 2048) return {64, 64};
     if (mma >= 1) {
         // split-bf16: the loop is bound by the operand split (VALU) and the LDS reads per MFMA, both of which shrink with
         // the wave tile - problems with enough tiles take the larger ones (bench_conv.py --mma --clips 8: 128x128 is
@@ -352,8 +357,8 @@ int k_tile_for(long M, int K, int ci, int bm, int bn)
     const int mma = tuning().mma_mode;
     // few-rows GEMMs (one frame of the lane head: 240 rows): deep K tiles.  With the frames of a clip batched (1200 rows) the
     // trunk plan wins in the staged-split arithmetic: 1024 -> 8192 174 vs 260 us, 4608 -> 1024 96 vs 146 us (bench_conv --only clipB)
-    if (M <= (mma == 3 ? 256 : 2048) && K >= 64) return (mma == 3 && tuning().deep_kt3 == 32) ? 32 : 64;
-    if (mma == 3) return BK;                                          // 37 KB of LDS per 64x64 workgroup: four per CU
+    if (M <= (staged(mma) ? 256 : 2048) && K >= 64) return (staged(mma) && tuning().deep_kt3 == 32) ? 32 : 64;
+    if (staged(mma)) return BK;                                          // 37 KB of LDS per 64x64 workgroup: four per CU
     if (mma >= 1 && bm == 64 && bn == 64 && ci % 32 == 0) return 32;
     return BK;
 }
@@ -374,7 +379,12 @@ ConvPlan plan_conv(long M, int Co, int K, bool has_ws, size_t ws_bytes)
     // split K until ~1250 workgroups are in flight (about 5 per CU), keeping >= 256 of K per split
     // K-tile-64 plans (M <= 2048: the head GEMMs) hold 70 KB of LDS per workgroup = 2 workgroups per CU, so ~512 tiles already
     // fill the chip in one round and a split only adds the reduce pass (hyper-net 1024 -> 8192 at 240 rows: 54 vs 62 us)
-    const bool deep = M <= (tn.mma_mode == 3 ? 256 : 2048) && K >= 64;
+    const bool deep = M <= (staged(tn.mma_mode) ? 256 : 2048) && K >= 64;
+    // Mode 4 does not split K on its own.  The split count follows the tile count, i.e. the batch: a stream step (one frame) and a clip
+    // (T frames) then sum an output's products in different groupings, the last bits differ, and the NEXT layer rounds them to bf16 -
+    // a bf16 ulp (4e-3) apart where a value sits at a rounding boundary.  Unsplit, an output's accumulation chain (16-deep MFMA steps
+    // in ascending K) is the same for every batch size, tile and K-tile depth: results are batch-invariant bit for bit.
+    if (tn.mma_mode == 4 && !tn.bf16_splitk) return p;
     if (has_ws && p.tiles < (deep ? 400 : 900)) {
         int splits = (int)min((long)8, max((long)1, (1250 + p.tiles / 2) / p.tiles));
         while (splits > 1 && K / splits < 256) --splits;
@@ -396,16 +406,17 @@ ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes,
     // deep K tiles for skinny (latency-bound) problems: few row tiles and K long enough to fill them
     p.bkt = tn.force_kt ? tn.force_kt : k_tile_for(M, K, g.Ci, t.bm, t.bn);
     p.mma = tn.mma_mode;
-    p.pf = p.mma == 3 ? ((tn.pf == 4 || tn.pf == 2) ? tn.pf : 1) : (p.mma == 0 && tn.pf == 4) ? 4 : 1;     // the instantiated ring depths
+    p.pf = staged(p.mma) ? ((tn.pf == 4 || tn.pf == 2) ? tn.pf : 1) : (p.mma == 0 && tn.pf == 4) ? 4 : 1;     // the instantiated ring depths
     // uniform-tap variant (the production tile only): the A-side channel count is a multiple of the K tile
     const bool uni = (g.Ci % p.bkt) == 0 && tn.uniform_tap;
     p.uni = uni && t.bm == 64 && t.bn == 64;
-    p.buf = p.uni && g.in_dil == 1 && tn.buf_loads && p.mma == 3;
-    p.taps3 = tn.taps3 && p.buf && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Ho == g.Hi && g.Wo == g.Wi &&
+    p.buf = p.uni && g.in_dil == 1 && tn.buf_loads && staged(p.mma);
+    // (the three-taps kernel exists in mode 3 only: mode 4 keeps these shapes on the generic kernel - or, one level up, on conv3p.hip)
+    p.taps3 = tn.taps3 && p.mma == 3 && p.buf && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Ho == g.Hi && g.Wo == g.Wi &&
               p.bkt == 16 && p.pf == 4 && g.Wi >= 2 && M * (long)g.Ci * 4 < 0x7fffffffL && (long)g.Co * K * 4 < 0x7fffffffL;
     // a Linear layer without epilogue extras: the tall-tile kernel where it applies to this plan's split count (linrows.hip)
     const bool linear = g.R == 1 && g.S == 1 && g.Hi == 1 && g.Wi == 1 && g.stride == 1 && g.pad == 0 && g.in_dil == 1;
-    if (linear && !extras && (p.rows = linrows_wm(M, K, g.Co, p.splits)) != 0) {
+    if (linear && !extras && (p.rows = linrows_wm(dgrad, M, K, g.Co, p.splits)) != 0) {
         p.bm = 160 * p.rows; p.bn = 128;
         p.tiles = ceil_div64(M, p.bm) * ceil_div64(g.Co, p.bn);
     }
@@ -416,7 +427,8 @@ ConvPick pick_conv(const ConvShape& g, bool dgrad, bool has_ws, size_t ws_bytes,
 int conv_kernel_name(const ConvPick& p, char* name, int cap)
 {
     static const char* const tf[2] = {"false", "true"};
-    const int n = p.rows  ? snprintf(name, (size_t)cap, LINROWS_NAME, tf[p.dgrad], p.rows)
+    const int n = p.rows  ? (p.mma == 4 ? snprintf(name, (size_t)cap, LINROWS_BF16_NAME, p.rows)
+                                        : snprintf(name, (size_t)cap, LINROWS_NAME, tf[p.dgrad], p.rows))
                 : p.taps3 ? snprintf(name, (size_t)cap, "conv3x3s1_kernel<%s>", tf[p.dgrad])
                           : snprintf(name, (size_t)cap, "conv_igemm_kernel<%d, %d, %s, %d, %s, %d, %d, %s>", p.bm, p.bn, tf[p.dgrad], p.bkt,
                                      tf[p.uni], p.mma, p.pf, tf[p.buf]);
@@ -448,6 +460,7 @@ template <bool DGRAD>
 int launch_conv(const float* X, const float* W, const float* bias, const float* addend, float* out, float* workspace,
                 size_t ws_bytes, ConvShape g, int relu, hipStream_t st, float* stats = nullptr)
 {
+    if (DGRAD && tuning().mma_mode == 4) return PHNET_ERR_ARG;      // the bf16 inference arithmetic is forward-only
     const ConvPick p = pick_conv(g, DGRAD, workspace != nullptr, ws_bytes, addend != nullptr || stats != nullptr);
     const long M = (long)g.N * g.Ho * g.Wo;
     const int K = g.R * g.S * g.Ci;
@@ -474,7 +487,8 @@ int launch_conv(const float* X, const float* W, const float* bias, const float* 
                            X, W, bias, addend, dst, g, relu, splits > 1 ? (float*)nullptr : stats);
     } else {
         const ConvLaunch a{X, W, bias, addend, dst, splits > 1 ? (float*)nullptr : stats, &g, relu, grid, st};
-        if (p.mma != 3) launch_conv_alt(p, a);
+        if (p.mma == 4) launch_conv_bf16(p, a);
+        else if (p.mma != 3) launch_conv_alt(p, a);
         else PHNET_LAUNCH_CONV_TILES(DGRAD);
     }
     if (splits > 1) {
@@ -507,6 +521,7 @@ PHNET_API int phnet_conv2d_kernel(int32_t dgrad, int32_t N, int32_t Hi, int32_t 
 {
     ConvShape g;
     if (!conv_args_ok(N, Hi, Wi, Ci, Co, R, S, stride, pad) || N < 1 || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
+    if (dgrad && tuning().mma_mode == 4) return PHNET_ERR_ARG;      // forward-only arithmetic: there is no such launch
     if (dgrad ? (stride > 2 || !dgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g)) : !fwd_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g))
         return PHNET_ERR_ARG;
     const ConvPick p = pick_conv(g, dgrad != 0, ws_bytes > 0, (size_t)ws_bytes, false);

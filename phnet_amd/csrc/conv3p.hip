@@ -14,7 +14,11 @@
 //    fragment reads, 36 MFMAs per barrier (a unit = filter row x 16-channel chunk: the 130 pixels m0-1 .. m0+128 of the
 //    shifted image row staged once - split into bf16 planes on the way - and multiplied by the three taps dx).
 //
-// Roofline: MFMA (bf16 pipe, 6 MFMAs per f32-exact product: 416.7 TFLOP/s algorithmic); algorithmic FLOP = 2 * M * Co * 9Ci.
+//  * conv3p_bf16_kernel is the same program on ONE plane per operand (arithmetic mode 4, the bf16 inference arithmetic: forward
+//    packing only): one 1 KB weight block per step and fragment, one A-side LDS plane, one MFMA per product.
+//
+// Roofline: MFMA (bf16 pipe, 6 MFMAs per f32-exact product: 416.7 TFLOP/s algorithmic; mode 4: one per product, 2.5 PFLOP/s);
+// algorithmic FLOP = 2 * M * Co * 9Ci.
 #include <cstdio>
 #include "igemm.h"
 #include "tuning.h"
@@ -32,14 +36,17 @@ struct P3Shape {
 constexpr int P3_BM = 128, P3_ROWS = P3_BM + 2, P3_THREADS = 256;      // columns per workgroup: 64 * FN (template)
 constexpr int P3_APITCH = 48;                                 // bytes: 16 bf16 + 16 pad (conflict-free ds_read_b128, igemm.h KContigPlanes)
 constexpr int P3_ZROW = P3_ROWS;                              // one more row per plane that stays zero: where border lanes read
-constexpr int P3_APLANE = (P3_ROWS + 1) * P3_APITCH, P3_AIMG = 3 * P3_APLANE;
+constexpr int P3_APLANE = (P3_ROWS + 1) * P3_APITCH;
 constexpr int P3_PFB = 3;                                     // weight fragments in flight, in steps (= one unit ahead)
-constexpr size_t P3_LDS = 2 * P3_AIMG + 3 * 512;
+// NP planes per operand: 3 = the exact split; 1 = the bf16 inference arithmetic (arithmetic mode 4, forward only): every element
+// rounded to bf16 once - the weights when they are packed, the pixels when they are staged - and ONE MFMA per product (igemm.h)
+constexpr size_t p3_lds(int np) { return (size_t)2 * np * P3_APLANE + np * 512; }
 
-// packed weights: [step q = (dy*CC + cc)*3 + dx][fragment j = n / 32][plane][lane] x 16 bytes
+// packed weights: [step q = (dy*CC + cc)*3 + dx][fragment j = n / 32][plane 0 .. NP-1][lane] x 16 bytes
 // lane (r = lane & 31, h = lane >> 5) holds k = 8h .. 8h+7 of the step's 16 channels for column n = 32j + r.
 struct P3PackJob { const float* w; unsigned char* dst; int Co, Ci, dgrad, pad_; long first; };   // `first`: index of the job's first item
 
+template <int NP>
 __device__ __forceinline__ void conv3p_pack_item(const float* __restrict__ w, unsigned char* __restrict__ packed, int Co, int Ci,
                                                  int dgrad, long i)
 {
@@ -59,26 +66,33 @@ __device__ __forceinline__ void conv3p_pack_item(const float* __restrict__ w, un
         v[e] = !dgrad ? w[(((long)n * 3 + dy) * 3 + dx) * Ci + k0 + e]
                       : w[(((long)(k0 + e) * 3 + (2 - dy)) * 3 + (2 - dx)) * Ci + n];
     }
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (NP == 1) {
+        *reinterpret_cast<u32x4*>(packed + (qj * 64 + lane) * 16) =
+            (u32x4){bf16_pair(v[0], v[1]), bf16_pair(v[2], v[3]), bf16_pair(v[4], v[5]), bf16_pair(v[6], v[7])};
+        return;
+    }
     unsigned hi[4], mid[4], lo[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) split3_pair(v[2 * e], v[2 * e + 1], hi[e], mid[e], lo[e]);
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     unsigned char* dst = packed + ((qj * 3) * 64 + lane) * 16;
     *reinterpret_cast<u32x4*>(dst) = (u32x4){hi[0], hi[1], hi[2], hi[3]};
     *reinterpret_cast<u32x4*>(dst + 1024) = (u32x4){mid[0], mid[1], mid[2], mid[3]};
     *reinterpret_cast<u32x4*>(dst + 2048) = (u32x4){lo[0], lo[1], lo[2], lo[3]};
 }
 
+template <int NP>
 __global__ __launch_bounds__(256) void conv3p_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ packed,
                                                           int Co, int Ci, int dgrad)
 {
     const int Ca = dgrad ? Co : Ci, Nn = dgrad ? Ci : Co;
     const long total = (long)9 * (Ca >> 4) * (Nn >> 5) * 64;          // (q, j, lane) triples
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total) conv3p_pack_item(w, packed, Co, Ci, dgrad, i);
+    if (i < total) conv3p_pack_item<NP>(w, packed, Co, Ci, dgrad, i);
 }
 
 // every 3x3 weight of the model in ONE launch: item i belongs to the job with the largest `first` <= i (jobs sorted by `first`)
+template <int NP>
 __global__ __launch_bounds__(256) void conv3p_pack_jobs_kernel(const P3PackJob* __restrict__ jobs, int njobs, long total)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -89,17 +103,21 @@ __global__ __launch_bounds__(256) void conv3p_pack_jobs_kernel(const P3PackJob* 
         if (jobs[mid].first <= i) lo = mid; else hi = mid - 1;
     }
     const P3PackJob jb = jobs[lo];
-    conv3p_pack_item(jb.w, jb.dst, jb.Co, jb.Ci, jb.dgrad, i - jb.first);
+    conv3p_pack_item<NP>(jb.w, jb.dst, jb.Co, jb.Ci, jb.dgrad, i - jb.first);
 }
 
-template <int FN>
-__global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
+template <int NP> struct P3Frag { typedef Frag3 type; };
+template <> struct P3Frag<1> { typedef bf16x8 type; };
+
+template <int FN, int NP>
+__device__ __forceinline__ void conv3p_tile(
     const float* __restrict__ X, const unsigned char* __restrict__ Bp, const float* __restrict__ bias,
-    const float* __restrict__ addend, float* __restrict__ out, P3Shape g, int relu, float* __restrict__ stats)
+    const float* __restrict__ addend, float* __restrict__ out, const P3Shape& g, int relu, float* __restrict__ stats, unsigned char* A3)
 {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    unsigned char* A3 = reinterpret_cast<unsigned char*>(lds);       // [2][3 planes][130 rows][48]
-    unsigned char* dump = A3 + 2 * P3_AIMG;                          // 3 x 512 bytes: where lanes without a third A chunk write
+    // A3: [2][NP planes][131 rows][48]
+    constexpr int P3_AIMG = NP * P3_APLANE;
+    typedef typename P3Frag<NP>::type Frag;
+    unsigned char* dump = A3 + 2 * P3_AIMG;                          // NP x 512 bytes: where lanes without a third A chunk write
 
     const int W = g.W, H = g.H, Ca = g.Ca;
     const int M = g.N * H * W;
@@ -114,7 +132,7 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
 
     constexpr unsigned OOB = 0x80000000u;
     __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)min((long)M * Ca * 4, (long)0x7fffffff), 0x00020000);
-    __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, 0, (int)min((long)9 * Ca * g.Nn * 6, (long)0x7fffffff), 0x00020000);
+    __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, 0, (int)min((long)9 * Ca * g.Nn * 2 * NP, (long)0x7fffffff), 0x00020000);
 
     // ---- A staging: 130 rows x 4 chunks = 520 float4: thread tid takes idx = tid, tid + 256 and (tid < 8) 512 + tid ----
     int a_off[3], a_ok[3], a_lds[3];
@@ -150,6 +168,12 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
         la_dy += wrap;
     };
     auto store_a = [&](int aoff, const f32x4 (&reg)[3]) {
+        if constexpr (NP == 1) {
+            store_bf16(A3 + aoff, a_lds[0], reg[0]);
+            store_bf16(A3 + aoff, a_lds[1], reg[1]);
+            if (wave0) store_bf16(a_lds[2] >= 0 ? A3 + aoff : dump, a_lds[2] >= 0 ? a_lds[2] : lane * 8, reg[2]);
+            return;
+        }
         store_split3<P3_APLANE>(A3 + aoff, a_lds[0], reg[0]);
         store_split3<P3_APLANE>(A3 + aoff, a_lds[1], reg[1]);
         if (wave0) {
@@ -164,15 +188,20 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
             *reinterpret_cast<u32x2*>(q + 2 * ps) = (u32x2){l0, l1};
         }
     };
-    // ---- B: the wave's fragment j of step q, three planes, straight into registers ----
+    // ---- B: the wave's fragment j of step q, NP planes (1 KB each), straight into registers ----
     const int jfrag = (n0 + wn) >> 5;
-    const int b_lane = (jfrag * 3 * 64 + lane) * 16;
-    const int b_step = NF * 3 * 64 * 16;                     // bytes per step
+    const int b_lane = (jfrag * NP * 64 + lane) * 16;
+    const int b_step = NF * NP * 64 * 16;                    // bytes per step
     int lb_q = u_begin * 3;                                   // next step to load
     const int q_end = u_end * 3;
-    auto load_b = [&](Frag3 (&f)[FN]) {
+    auto load_b = [&](Frag (&f)[FN]) {
         const bool ok = lb_q < q_end;
         const int off = b_lane + lb_q * b_step;
+        if constexpr (NP == 1) {
+#pragma unroll
+            for (int jn = 0; jn < FN; ++jn)
+                f[jn] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, ok ? off + jn * 1024 : (int)OOB, 0, 0));
+        } else
 #pragma unroll
         for (int jn = 0; jn < FN; ++jn) {
             f[jn].hi = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, ok ? off + jn * 3072 : (int)OOB, 0, 0));
@@ -216,14 +245,14 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
         a_rel[f][1] = (rr + 1) * P3_APITCH + hb;
         a_rel[f][2] = (px == W - 1 ? P3_ZROW : rr + 2) * P3_APITCH + hb;
     }
-    for (int i = tid; i < 2 * 3 * (P3_APITCH / 4); i += P3_THREADS) {          // the zero rows of both images, all planes
-        const int img = i / (3 * (P3_APITCH / 4)), rem = i % (3 * (P3_APITCH / 4)), pl = rem / (P3_APITCH / 4), w4 = rem % (P3_APITCH / 4);
+    for (int i = tid; i < 2 * NP * (P3_APITCH / 4); i += P3_THREADS) {         // the zero rows of both images, all planes
+        const int img = i / (NP * (P3_APITCH / 4)), rem = i % (NP * (P3_APITCH / 4)), pl = rem / (P3_APITCH / 4), w4 = rem % (P3_APITCH / 4);
         *reinterpret_cast<unsigned*>(A3 + img * P3_AIMG + pl * P3_APLANE + P3_ZROW * P3_APITCH + w4 * 4) = 0u;
     }
 
     if (u_begin < u_end) {
         f32x4 a_reg[3];
-        Frag3 bq[P3_PFB][FN];
+        Frag bq[P3_PFB][FN];
         load_a(a_reg);
 #pragma unroll
         for (int d = 0; d < P3_PFB; ++d) load_b(bq[d]);
@@ -233,15 +262,19 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
         int aoff = 0;
         auto step = [&](auto DX) {
             constexpr int dxi = decltype(DX)::value;
-            Frag3 a[2];
+            Frag a[2];
 #pragma unroll
             for (int f = 0; f < 2; ++f) {
                 const unsigned char* p = A3 + aoff + a_rel[f][dxi];
-                a[f].hi = *reinterpret_cast<const bf16x8*>(p);
-                a[f].mid = *reinterpret_cast<const bf16x8*>(p + P3_APLANE);
-                a[f].lo = *reinterpret_cast<const bf16x8*>(p + 2 * P3_APLANE);
+                if constexpr (NP == 1) a[f] = *reinterpret_cast<const bf16x8*>(p);
+                else {
+                    a[f].hi = *reinterpret_cast<const bf16x8*>(p);
+                    a[f].mid = *reinterpret_cast<const bf16x8*>(p + P3_APLANE);
+                    a[f].lo = *reinterpret_cast<const bf16x8*>(p + 2 * P3_APLANE);
+                }
             }
-            mma3_step<2, FN>(a, bq[dxi], acc);
+            if constexpr (NP == 1) mma1_step<2, FN>(a, bq[dxi], acc);
+            else mma3_step<2, FN>(a, bq[dxi], acc);
             load_b(bq[dxi]);                                  // the slot takes the fragment three steps ahead
         };
         for (int u = u_begin; u < u_end; ++u) {
@@ -288,6 +321,26 @@ __global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
                 if (m < M) dst[(size_t)m * g.Nn + n] = (final_pass && relu) ? fmaxf(acc[f][jn][e], 0.f) : acc[f][jn][e];
             }
     }
+}
+
+template <int FN>
+__global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_kernel(
+    const float* __restrict__ X, const unsigned char* __restrict__ Bp, const float* __restrict__ bias,
+    const float* __restrict__ addend, float* __restrict__ out, P3Shape g, int relu, float* __restrict__ stats)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    conv3p_tile<FN, 3>(X, Bp, bias, addend, out, g, relu, stats, reinterpret_cast<unsigned char*>(lds));
+}
+
+// the same program on one-plane operands: arithmetic mode 4 (forward packing only).  (Occupancy as above: what a third of the LDS
+// would allow beyond it has not been measured.)
+template <int FN>
+__global__ __launch_bounds__(P3_THREADS, FN == 1 ? 3 : 2) void conv3p_bf16_kernel(
+    const float* __restrict__ X, const unsigned char* __restrict__ Bp, const float* __restrict__ bias,
+    const float* __restrict__ addend, float* __restrict__ out, P3Shape g, int relu, float* __restrict__ stats)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    conv3p_tile<FN, 1>(X, Bp, bias, addend, out, g, relu, stats, reinterpret_cast<unsigned char*>(lds));
 }
 
 // out[i] = sum_z part[z][i] (+bias) (+addend) (relu); optionally the BatchNorm statistics rows of the result (conv.hip's
@@ -363,7 +416,9 @@ P3Plan p3_plan(long M, int Ca, int Nn, size_t ws_bytes)
     p.tiles = cdiv(M, P3_BM) * (Nn / (64 * p.fn));
     const int units = 3 * (Ca / 16);
     int splits = 1;
-    if (ws_bytes > 0 && p.tiles * 2 <= tuning().p3_target) {
+    // (arithmetic mode 4 does not split K on its own: batch-invariant results, conv.hip plan_conv)
+    const bool may_split = tuning().mma_mode != 4 || tuning().bf16_splitk;
+    if (may_split && ws_bytes > 0 && p.tiles * 2 <= tuning().p3_target) {
         splits = (int)min((long)8, (long)tuning().p3_target / p.tiles);
         while (splits > 1 && units / splits < 4) --splits;                     // >= 4 units (192 of K) per split
         while (splits > 1 && (size_t)splits * M * Nn * sizeof(float) > ws_bytes) --splits;
@@ -376,7 +431,8 @@ P3Plan p3_plan(long M, int Ca, int Nn, size_t ws_bytes)
 // the instantiation the launch switch of phnet_conv3p_fwd picks for a plan
 int p3_kernel_name(const P3Plan& p, char* name, int cap)
 {
-    return snprintf(name, (size_t)cap, "conv3p_kernel<%d>", p.fn) < cap ? PHNET_OK : PHNET_ERR_ARG;
+    return snprintf(name, (size_t)cap, tuning().mma_mode == 4 ? "conv3p_bf16_kernel<%d>" : "conv3p_kernel<%d>", p.fn) < cap ? PHNET_OK
+                                                                                                                           : PHNET_ERR_ARG;
 }
 
 bool p3_applies(long M, int Ca, int Nn)
@@ -401,8 +457,21 @@ PHNET_API int phnet_conv3p_pack(const float* w, void* packed, int32_t Co, int32_
     const int Ca = dgrad ? Co : Ci, Nn = dgrad ? Ci : Co;
     if ((Ca % 16) || (Nn % 32)) return PHNET_ERR_ARG;
     const long total = (long)9 * (Ca / 16) * (Nn / 32) * 64;
-    hipLaunchKernelGGL(conv3p_pack_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(conv3p_pack_kernel<3>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        w, (unsigned char*)packed, Co, Ci, dgrad);
+    return phnet_launch_status();
+}
+
+// The one-plane image of arithmetic mode 4: every weight rounded to bf16 once, same fragment order, one 1 KB block per step and
+// fragment - exactly a third of phnet_conv3p_packed_bytes.  Forward packing only (the mode has no data gradient).
+PHNET_API uint64_t phnet_conv3p_packed_bytes_bf16(int32_t Co, int32_t Ci) { return (uint64_t)9 * Co * Ci * 2; }
+
+PHNET_API int phnet_conv3p_pack_bf16(const float* w, void* packed, int32_t Co, int32_t Ci, void* stream)
+{
+    if (!w || !packed || Co < 32 || Ci < 16 || (Ci % 16) || (Co % 32)) return PHNET_ERR_ARG;
+    const long total = (long)9 * (Ci / 16) * (Co / 32) * 64;
+    hipLaunchKernelGGL(conv3p_pack_kernel<1>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       w, (unsigned char*)packed, Co, Ci, 0);
     return phnet_launch_status();
 }
 
@@ -411,7 +480,16 @@ PHNET_API int phnet_conv3p_pack(const float* w, void* packed, int32_t Co, int32_
 PHNET_API int phnet_conv3p_pack_jobs(const void* jobs, int32_t njobs, int64_t total, void* stream)
 {
     if (!jobs || njobs < 1 || total < 1) return PHNET_ERR_ARG;
-    hipLaunchKernelGGL(conv3p_pack_jobs_kernel, dim3((unsigned)cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(conv3p_pack_jobs_kernel<3>, dim3((unsigned)cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const P3PackJob*)jobs, njobs, (long)total);
+    return phnet_launch_status();
+}
+
+// the same job table (every record with dgrad = 0) packed into one-plane images
+PHNET_API int phnet_conv3p_pack_jobs_bf16(const void* jobs, int32_t njobs, int64_t total, void* stream)
+{
+    if (!jobs || njobs < 1 || total < 1) return PHNET_ERR_ARG;
+    hipLaunchKernelGGL(conv3p_pack_jobs_kernel<1>, dim3((unsigned)cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const P3PackJob*)jobs, njobs, (long)total);
     return phnet_launch_status();
 }
@@ -448,11 +526,18 @@ PHNET_API int phnet_conv3p_fwd(const float* x, const void* packed, const float* 
     P3Shape g{N, H, W, Ca, Nn, p.splits, p.units_per_split};
     float* dst = p.splits > 1 ? (float*)workspace : y;
     hipStream_t st = (hipStream_t)stream;
-    if (p.fn == 2)
-        hipLaunchKernelGGL(conv3p_kernel<2>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), P3_LDS, st,
+    if (tuning().mma_mode == 4) {                           // `packed` is the one-plane image of phnet_conv3p_pack_bf16
+        if (p.fn == 2)
+            hipLaunchKernelGGL(conv3p_bf16_kernel<2>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), p3_lds(1), st,
+                               x, (const unsigned char*)packed, bias, addend, dst, g, relu, p.splits > 1 ? (float*)nullptr : stats);
+        else
+            hipLaunchKernelGGL(conv3p_bf16_kernel<1>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), p3_lds(1), st,
+                               x, (const unsigned char*)packed, bias, addend, dst, g, relu, p.splits > 1 ? (float*)nullptr : stats);
+    } else if (p.fn == 2)
+        hipLaunchKernelGGL(conv3p_kernel<2>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), p3_lds(3), st,
                            x, (const unsigned char*)packed, bias, addend, dst, g, relu, p.splits > 1 ? (float*)nullptr : stats);
     else
-        hipLaunchKernelGGL(conv3p_kernel<1>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), P3_LDS, st,
+        hipLaunchKernelGGL(conv3p_kernel<1>, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(P3_THREADS), p3_lds(3), st,
                            x, (const unsigned char*)packed, bias, addend, dst, g, relu, p.splits > 1 ? (float*)nullptr : stats);
     if (p.splits > 1) {
         const long total4 = M * Nn / 4;

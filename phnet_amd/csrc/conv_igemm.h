@@ -1,5 +1,5 @@
-// conv_igemm_kernel and the macro ladder that launches it: what conv.hip (arithmetic mode 3) and linear_bwd.hip (modes 0 / 1 / 2)
-// share.  The instantiations are split over two sources only because they are the slowest thing in the build; the decision
+// conv_igemm_kernel and the macro ladder that launches it: what conv.hip (arithmetic mode 3), linear_bwd.hip (modes 0 / 1 / 2) and
+// conv_bf16.hip (mode 4, forward only) share.  The instantiations are split over two sources only because they are the slowest thing in the build; the decision
 // (pick_conv), the name (conv_kernel_name) and the launch arithmetic (launch_conv) stay in conv.hip.  Internal, not part of the C-ABI.
 #pragma once
 #include "igemm_tile.h"
@@ -48,16 +48,19 @@ struct ConvLaunch {
     hipStream_t st;
 };
 
-// linear_bwd.hip: the launch for p.mma != 3
+// linear_bwd.hip: the launch for p.mma 0 / 1 / 2
 void launch_conv_alt(const ConvPick& p, const ConvLaunch& a);
+// conv_bf16.hip: the launch for p.mma == 4 (bf16 inference arithmetic: forward only, p.dgrad is false)
+void launch_conv_bf16(const ConvPick& p, const ConvLaunch& a);
 
 // The ladder from a pick to its instantiation, for a function that has p (ConvPick), a (ConvLaunch) and g (ConvShape) in scope.
 // The including source defines the arithmetic rungs it builds: PHNET_LAUNCH_CONV_(DGRAD_, BM_, BN_, BKT_, UNI_).
 #define PHNET_LAUNCH_CONV____(DGRAD_, BM_, BN_, BKT_, UNI_, MMA_, PF_, BUF_)                                            \
     do {                                                                                                                \
-        constexpr size_t lds_ = MMA_ == 3                                                                               \
-            ? 2 * (size_t)(KContigPlanes<BM_, BKT_>::BYTES +                                                            \
-                           (DGRAD_ ? KStridedPlanes<BN_, BKT_>::BYTES : KContigPlanes<BN_, BKT_>::BYTES))               \
+        constexpr int np_ = MMA_ == 4 ? 1 : 3;                                                                          \
+        constexpr size_t lds_ = (MMA_ == 3 || MMA_ == 4)                                                                \
+            ? 2 * (size_t)(KContigPlanes<BM_, BKT_, np_>::BYTES +                                                       \
+                           (DGRAD_ ? KStridedPlanes<BN_, BKT_, np_>::BYTES : KContigPlanes<BN_, BKT_, np_>::BYTES))     \
             : 2 * (size_t)(KContigTile<BM_, BKT_>::FLOATS +                                                             \
                            (DGRAD_ ? KStridedTile<BN_, BKT_>::FLOATS : KContigTile<BN_, BKT_>::FLOATS)) * 4;            \
         static bool attr_set_ = false;                                                                                  \

@@ -598,6 +598,7 @@ PHNET_API int phnet_conv2d_wgrad_kernel(int32_t N, int32_t Hi, int32_t Wi, int32
 {
     WgradShape g;
     if (!wgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g) || !name || name_cap < 1 || !splits) return PHNET_ERR_ARG;
+    if (tuning().mma_mode == 4) return PHNET_ERR_ARG;               // the bf16 inference arithmetic is forward-only
     const WgradPick p = pick_wgrad(g, has_dbias != 0, ws_bytes > 0, ws_bytes);
     *splits = (int32_t)p.splits;
     return wgrad_kernel_name(p, name, name_cap);
@@ -613,6 +614,7 @@ PHNET_API int phnet_conv2d_wgrad(const float* dy, const float* x, float* dw, flo
 {
     WgradShape g;
     if (!wgrad_shape(N, Hi, Wi, Ci, Co, R, S, stride, pad, &g) || !dy || !x || !dw) return PHNET_ERR_ARG;
+    if (tuning().mma_mode == 4) return PHNET_ERR_ARG;               // the bf16 inference arithmetic is forward-only
     const WgradPick p = pick_wgrad(g, dbias != nullptr, workspace != nullptr, ws_bytes);
     const long P = (long)N * g.Ho * g.Wo, NC = (long)R * S * Ci;
     hipStream_t st = (hipStream_t)stream;

@@ -150,17 +150,18 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // K-contiguous bf16 plane [rows][BKT] with a 16-byte pad per row: the 16 lanes of a ds_read_b128 lane group sit on 16
 // distinct 16-byte slots of the 256-byte bank row for BKT = 16, 32 and 64 (row pitches 48, 80, 144 bytes: odd multiples of 16)
-template <int ROWS, int BKT> struct KContigPlanes {
+// (NP planes per tile: 3 for the exact split, 1 for the bf16 inference arithmetic below - the pitches are the same)
+template <int ROWS, int BKT, int NP = 3> struct KContigPlanes {
     static constexpr int PITCH = BKT * 2 + 16;                 // bytes
     static constexpr int PLANE = ROWS * PITCH;                 // bytes per plane
-    static constexpr int BYTES = 3 * PLANE;
+    static constexpr int BYTES = NP * PLANE;
 };
 // K-strided bf16 plane [BKT][cols] with 64 bytes of pad per row: the 4 k-rows x 64 bytes that one half wave fetches with
 // ds_read_b64_tr_b16 then fall on four distinct quarters of the bank row (pitch = 64 mod 256 for 128 columns, 192 for 64)
-template <int COLS, int BKT> struct KStridedPlanes {
+template <int COLS, int BKT, int NP = 3> struct KStridedPlanes {
     static constexpr int PITCH = COLS * 2 + 64;
     static constexpr int PLANE = BKT * PITCH;
-    static constexpr int BYTES = 3 * PLANE;
+    static constexpr int BYTES = NP * PLANE;
 };
 
 // two f32 -> three packed bf16 pairs (hi, mid, lo) with x = hi + mid + lo exactly
@@ -239,6 +240,48 @@ __device__ __forceinline__ void mma3_step(const Frag3 (&a)[FM], const Frag3 (&b)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i].hi, b[j].mid, acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i].hi, b[j].hi, acc[i][j], 0, 0, 0);
         }
+}
+
+// ---- MMA = 4: bf16 inference arithmetic (forward only) --------------------------------------------------------------------
+// Every operand element is rounded to bf16 ONCE (round to nearest even: the conversion split3_pair uses for its hi term) while
+// the tile is staged; a product of two bf16 values is exact in f32 (8 + 8 mantissa bits) and is summed in the f32 accumulators of
+// v_mfma_f32_32x32x16_bf16: ONE MFMA per 16-deep product instead of six, one LDS plane per operand tile instead of three, a
+// convert instead of the split.  Plane pitches, lane-to-k mapping and the ds_read_b64_tr_b16 constraints are those of MMA = 3.
+__device__ __forceinline__ unsigned bf16_pair(float x0, float x1) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, bf16x2));
+}
+
+// four consecutive elements (one staged float4) -> 8 bytes of the single plane at byte offset `off`
+__device__ __forceinline__ void store_bf16(unsigned char* plane, int off, const f32x4& v) {
+    *reinterpret_cast<u32x2*>(plane + off) = (u32x2){bf16_pair(v.x, v.y), bf16_pair(v.z, v.w)};
+}
+
+template <int F, int PITCH>
+__device__ __forceinline__ void read_kcontig1(const unsigned char* plane, int lane, int ks, bf16x8 (&frag)[F]) {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int f = 0; f < F; ++f) frag[f] = *reinterpret_cast<const bf16x8*>(plane + (f * 32 + r) * PITCH + 32 * ks + 16 * h);
+}
+
+// as read_kstrided3: EXEC must be all ones (no divergence, no ragged-tail early exit around this call)
+template <int F, int PITCH>
+__device__ __forceinline__ void read_kstrided1(const unsigned char* plane, int lane, int ks, bf16x8 (&frag)[F]) {
+    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
+    const int row = 16 * ks + 8 * (g >> 1) + q;
+    const int colb = (16 * (g & 1) + 4 * pp) * 2;
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const unsigned char* p = plane + row * PITCH + f * 64 + colb;
+        frag[f] = tr_read8(p, p + 4 * PITCH);
+    }
+}
+
+template <int FM, int FN>
+__device__ __forceinline__ void mma1_step(const bf16x8 (&a)[FM], const bf16x8 (&b)[FN], f32x16 (&acc)[FM][FN]) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
 }
 
 template <int MMA, int FM, int FN>

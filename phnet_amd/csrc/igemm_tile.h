@@ -34,6 +34,9 @@ __device__ __forceinline__ unsigned xcd_remap_striped(unsigned bid, unsigned nbl
 // out-of-range element is simply given an offset past the end of the tensor and the hardware returns zeros - no 64-bit
 // address arithmetic, no validity select when the tile is written to LDS (the loop is bound by its vector instruction
 // count: 90 per 6 MFMAs before, of which 44 are the split).
+// MMA: the arithmetic (igemm.h) - 0 f32-input MFMA, 1 / 2 bf16 splits in registers (f32 LDS images), 3 the exact split staged as
+// three bf16 planes, 4 the bf16 inference arithmetic: ONE staged bf16 plane per operand, one MFMA per product (forward launches only;
+// staging, ring, buffer loads and epilogues are mode 3's).
 // DIL (needs B_DGRAD && UNI && !BUF; the caller guarantees g.in_dil == 2 and a filter of at most 16 taps, R, S <= 16:
 // conv_igemm_kernel branches to this instantiation at run time and keeps the plain one for every other problem): the data
 // gradient of a stride-2 convolution gathers from a dY image dilated by 2, so a dX pixel of parity class (y & 1, x & 1) can use
@@ -64,10 +67,12 @@ __device__ __forceinline__ void igemm_tile(
     float* As = lds;
     float* Bs = lds + 2 * A_FLOATS;
     // MMA = 3: bf16 planes instead of f32 images (igemm.h)
-    constexpr bool S3 = MMA == 3;
-    typedef KContigPlanes<BM, BKT> AP3;
-    typedef KContigPlanes<BN, BKT> BP3C;
-    typedef KStridedPlanes<BN, BKT> BP3S;
+    // MMA = 4: ONE bf16 plane per operand (the bf16 inference arithmetic, igemm.h) - same pitches, same offsets inside a plane
+    constexpr bool S3 = MMA == 3, S1 = MMA == 4;
+    constexpr int NP = S1 ? 1 : 3;
+    typedef KContigPlanes<BM, BKT, NP> AP3;
+    typedef KContigPlanes<BN, BKT, NP> BP3C;
+    typedef KStridedPlanes<BN, BKT, NP> BP3S;
     constexpr int B3_BYTES = B_DGRAD ? BP3S::BYTES : BP3C::BYTES;
     unsigned char* A3 = reinterpret_cast<unsigned char*>(lds);
     unsigned char* B3 = A3 + 2 * AP3::BYTES;
@@ -325,6 +330,7 @@ __device__ __forceinline__ void igemm_tile(
                 v.z = a_relu[i].z > 0.f ? v.z : 0.f; v.w = a_relu[i].w > 0.f ? v.w : 0.f;
             }
             if (S3) store_split3<AP3::PLANE>(a3, (a_row + ROWS_PER_PASS * i) * AP3::PITCH + a_chunk * 8, v);
+            else if (S1) store_bf16(a3, (a_row + ROWS_PER_PASS * i) * AP3::PITCH + a_chunk * 8, v);
             else
             *reinterpret_cast<f32x4*>(a + (a_row + ROWS_PER_PASS * i) * A_PITCH + a_chunk * 4) = v;
         }
@@ -333,6 +339,7 @@ __device__ __forceinline__ void igemm_tile(
             for (int i = 0; i < B_LOADS; ++i) {
                 const f32x4 v = BUF ? b_reg[i] : ((mask >> (16 + i)) & 1u ? b_reg[i] : zero);
                 if (S3) store_split3<BP3C::PLANE>(b3, (a_row + ROWS_PER_PASS * i) * BP3C::PITCH + a_chunk * 8, v);
+                else if (S1) store_bf16(b3, (a_row + ROWS_PER_PASS * i) * BP3C::PITCH + a_chunk * 8, v);
                 else *reinterpret_cast<f32x4*>(b + (a_row + ROWS_PER_PASS * i) * B_PITCH + a_chunk * 4) = v;
             }
         } else {
@@ -340,6 +347,7 @@ __device__ __forceinline__ void igemm_tile(
             for (int i = 0; i < B_LOADS; ++i) {
                 const f32x4 v = BUF ? b_reg[i] : ((mask >> (16 + i)) & 1u ? b_reg[i] : zero);
                 if (S3) store_split3<BP3S::PLANE>(b3, b_kk[i] * BP3S::PITCH + b_ch[i] * 8, v);
+                else if (S1) store_bf16(b3, b_kk[i] * BP3S::PITCH + b_ch[i] * 8, v);
                 else *reinterpret_cast<f32x4*>(b + b_kk[i] * B_PITCH + b_ch[i] * 4) = v;
             }
         }
@@ -378,6 +386,18 @@ __device__ __forceinline__ void igemm_tile(
             }
             return;
         }
+        if (S1) {
+            // (no early exit on a ragged K tail either: the tail of the tile is staged as zeros)
+#pragma unroll
+            for (int ks = 0; ks < BKT / BK; ++ks) {
+                bf16x8 a[FM], b[FN];
+                read_kcontig1<FM, AP3::PITCH>(A3 + buf * AP3::BYTES + wm * AP3::PITCH, lane, ks, a);
+                if (!B_DGRAD) read_kcontig1<FN, BP3C::PITCH>(B3 + buf * B3_BYTES + wn * BP3C::PITCH, lane, ks, b);
+                else read_kstrided1<FN, BP3S::PITCH>(B3 + buf * B3_BYTES + wn * 2, lane, ks, b);
+                mma1_step<FM, FN>(a, b, acc);
+            }
+            return;
+        }
 #pragma unroll
         for (int ks = 0; ks < BKT / BK; ++ks) {
             if (BKT > BK && kt + ks * BK >= k_end) break;              // ragged K tail of a deep tile
@@ -385,7 +405,7 @@ __device__ __forceinline__ void igemm_tile(
             read_kcontig<FM, A_PITCH>(As + buf * A_FLOATS + wm * A_PITCH, lane, ks, a);
             if (!B_DGRAD) read_kcontig<FN, B_PITCH>(Bs + buf * B_FLOATS + wn * B_PITCH, lane, ks, b);
             else read_kstrided<FN, B_PITCH>(Bs + buf * B_FLOATS + wn, lane, ks, b);
-            mma_any<S3 ? 0 : MMA, FM, FN>(a, b, acc);
+            mma_any<(S3 || S1) ? 0 : MMA, FM, FN>(a, b, acc);
         }
     };
 

@@ -66,6 +66,7 @@ static int linear_bwd_kernel_name(const LinearBwdPick& p, char* name, int cap)
 PHNET_API int phnet_linear_bwd_kernel(int32_t M, int32_t K, int32_t N, int32_t has_relu_mask, char* name, int32_t name_cap)
 {
     if (!linear_bwd_fusable(M, K, N) || !name || name_cap < 1) return PHNET_ERR_ARG;
+    if (tuning().mma_mode == 4) return PHNET_ERR_ARG;               // the bf16 inference arithmetic is forward-only
     return linear_bwd_kernel_name(pick_linear_bwd(N, has_relu_mask != 0), name, name_cap);
 }
 
@@ -77,6 +78,7 @@ PHNET_API int phnet_linear_bwd(const float* dy, const float* x, const float* w, 
                                float* dbias, int32_t M, int32_t K, int32_t N, int32_t accumulate, void* stream)
 {
     if (!linear_bwd_fusable(M, K, N) || !dy || !x || !w || !dx || !dw) return PHNET_ERR_ARG;
+    if (tuning().mma_mode == 4) return PHNET_ERR_ARG;               // the bf16 inference arithmetic is forward-only
     ConvShape g{};
     g.N = M; g.Hi = 1; g.Wi = 1; g.Ci = N;              // A side = dY rows, N channels
     g.Ho = 1; g.Wo = 1; g.Co = K;                       // output = dX

@@ -34,7 +34,9 @@ struct RowsShape {
     int tiles_m;
 };
 
-template <bool DGRAD, int WM> struct RowsCfg {
+// NP: bf16 planes per staged operand - 3: the exact split (mode 3), 1: the bf16 inference arithmetic (mode 4, forward only: one convert
+// per element pair in the producers, one fragment read and one MFMA per product in the consumers; a third of the LDS)
+template <bool DGRAD, int WM, int NP = 3> struct RowsCfg {
     static constexpr int TM = WM * R_FM * 32;                // 160 | 320 rows per workgroup
     static constexpr int CONSUMERS = 4 * WM;
     static constexpr int NT = (CONSUMERS + R_PRODUCERS) * 64;
@@ -42,23 +44,22 @@ template <bool DGRAD, int WM> struct RowsCfg {
     static constexpr int A_ROWS = A_LOADS * 64;              // rows of the staged A image (160 -> 192: the last 32 are staged as zeros, never read)
     static constexpr int B_LOADS = 2;                        // 128 x 16 floats
     static constexpr int PF = WM == 2 ? 3 : 4;               // producer register ring: K steps in flight per thread (7 | 5 float4 each)
-    typedef KContigPlanes<A_ROWS, BK> AP;
-    typedef KContigPlanes<R_TN, BK> BPC;
-    typedef KStridedPlanes<R_TN, BK> BPS;
+    typedef KContigPlanes<A_ROWS, BK, NP> AP;
+    typedef KContigPlanes<R_TN, BK, NP> BPC;
+    typedef KStridedPlanes<R_TN, BK, NP> BPS;
     static constexpr int B_PITCH = DGRAD ? BPS::PITCH : BPC::PITCH;
     static constexpr int B_PLANE = DGRAD ? BPS::PLANE : BPC::PLANE;
-    static constexpr int STAGE = AP::BYTES + 3 * B_PLANE;    // A image | B image
-    static constexpr int LDS = 2 * STAGE;                    // 92 KB | 129 KB (forward)
+    static constexpr int STAGE = AP::BYTES + NP * B_PLANE;   // A image | B image
+    static constexpr int LDS = 2 * STAGE;                    // 92 KB | 129 KB (forward, three planes)
 };
 
-template <bool DGRAD, int WM>
-__global__ __launch_bounds__((RowsCfg<DGRAD, WM>::NT)) void linrows_kernel(const float* __restrict__ A, const float* __restrict__ W,
-                                                                         const float* __restrict__ bias, float* __restrict__ out,
-                                                                         RowsShape g, int relu)
+template <bool DGRAD, int WM, int NP>
+__device__ __forceinline__ void linrows_tile(const float* __restrict__ A, const float* __restrict__ W, const float* __restrict__ bias,
+                                             float* __restrict__ out, const RowsShape& g, int relu, unsigned char* lds_raw)
 {
-    typedef RowsCfg<DGRAD, WM> C;
+    typedef RowsCfg<DGRAD, WM, NP> C;
     typedef typename C::AP AP;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];               // [buffer 0..1][A planes | B planes]
+    static_assert(NP == 3 || (NP == 1 && !DGRAD), "three planes, or the forward-only one-plane arithmetic");
     const int M = g.M, K = g.K, N = g.N;
     const unsigned tile = xcd_remap(blockIdx.x, gridDim.x);
     // row tiles run fastest: the workgroups that share an L2 share weight columns and cover all rows
@@ -113,9 +114,15 @@ __global__ __launch_bounds__((RowsCfg<DGRAD, WM>::NT)) void linrows_kernel(const
         };
         auto store_step = [&](int buf_off, const f32x4 (&reg)[NL]) {
 #pragma unroll
-            for (int i = 0; i < C::A_LOADS; ++i) store_split3<AP::PLANE>(lds_raw + buf_off, a_lds[i], reg[i]);
+            for (int i = 0; i < C::A_LOADS; ++i) {
+                if constexpr (NP == 1) store_bf16(lds_raw + buf_off, a_lds[i], reg[i]);
+                else store_split3<AP::PLANE>(lds_raw + buf_off, a_lds[i], reg[i]);
+            }
 #pragma unroll
-            for (int i = 0; i < C::B_LOADS; ++i) store_split3<C::B_PLANE>(lds_raw + buf_off + AP::BYTES, b_lds[i], reg[C::A_LOADS + i]);
+            for (int i = 0; i < C::B_LOADS; ++i) {
+                if constexpr (NP == 1) store_bf16(lds_raw + buf_off + AP::BYTES, b_lds[i], reg[C::A_LOADS + i]);
+                else store_split3<C::B_PLANE>(lds_raw + buf_off + AP::BYTES, b_lds[i], reg[C::A_LOADS + i]);
+            }
         };
 #pragma unroll
         for (int d = 0; d < C::PF; ++d) load_step(ring[d]);
@@ -158,11 +165,18 @@ __global__ __launch_bounds__((RowsCfg<DGRAD, WM>::NT)) void linrows_kernel(const
         int o = 0;
         __syncthreads();                                     // step 0 is staged
         for (int t = 0; t < nsteps; ++t) {
-            Frag3 fa[R_FM], fb[1];
-            if (!DGRAD) read_kcontig3<1, C::B_PITCH, C::B_PLANE>(b_src + o, lane, 0, fb);
-            else read_kstrided3<1, C::B_PITCH, C::B_PLANE>(b_src + o, lane, 0, fb);
-            read_kcontig3<R_FM, AP::PITCH, AP::PLANE>(a_src + o, lane, 0, fa);
-            mma3_step<R_FM, 1>(fa, fb, acc);
+            if constexpr (NP == 1) {
+                bf16x8 fa[R_FM], fb[1];
+                read_kcontig1<1, C::B_PITCH>(b_src + o, lane, 0, fb);
+                read_kcontig1<R_FM, AP::PITCH>(a_src + o, lane, 0, fa);
+                mma1_step<R_FM, 1>(fa, fb, acc);
+            } else {
+                Frag3 fa[R_FM], fb[1];
+                if (!DGRAD) read_kcontig3<1, C::B_PITCH, C::B_PLANE>(b_src + o, lane, 0, fb);
+                else read_kstrided3<1, C::B_PITCH, C::B_PLANE>(b_src + o, lane, 0, fb);
+                read_kcontig3<R_FM, AP::PITCH, AP::PLANE>(a_src + o, lane, 0, fa);
+                mma3_step<R_FM, 1>(fa, fb, acc);
+            }
             __syncthreads();
             o = C::STAGE - o;
         }
@@ -180,13 +194,33 @@ __global__ __launch_bounds__((RowsCfg<DGRAD, WM>::NT)) void linrows_kernel(const
     }
 }
 
+template <bool DGRAD, int WM>
+__global__ __launch_bounds__((RowsCfg<DGRAD, WM>::NT)) void linrows_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                                         const float* __restrict__ bias, float* __restrict__ out,
+                                                                         RowsShape g, int relu)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];               // [buffer 0..1][A planes | B planes]
+    linrows_tile<DGRAD, WM, 3>(A, W, bias, out, g, relu, lds_raw);
+}
+
+// the forward in the bf16 inference arithmetic (mode 4): same tiles, same schedule, one plane
+template <int WM>
+__global__ __launch_bounds__((RowsCfg<false, WM>::NT)) void linrows_bf16_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                                              const float* __restrict__ bias, float* __restrict__ out,
+                                                                              RowsShape g, int relu)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    linrows_tile<false, WM, 1>(A, W, bias, out, g, relu, lds_raw);
+}
+
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
-// what the kernel itself needs: the staged-split arithmetic, whole 16-deep steps, float4 columns, 32-bit byte offsets with room for
+// what the kernel itself needs: a staged arithmetic (mode 3, or mode 4 for the forward), whole 16-deep steps, float4 columns, 32-bit byte offsets with room for
 // the rows of a ragged last tile
-bool rows_ok(long M, int K, int N)
+bool rows_ok(bool dgrad, long M, int K, int N)
 {
-    return tuning().mma_mode == 3 && M >= 1 && K >= BK && (K % BK) == 0 && N >= 4 && (N & 3) == 0 &&
+    const int mma = tuning().mma_mode;
+    return (mma == 3 || (mma == 4 && !dgrad)) && M >= 1 && K >= BK && (K % BK) == 0 && N >= 4 && (N & 3) == 0 &&
            (M + 320) * K * 4 < 0x7fffffffL && (long)N * K * 4 < 0x7fffffffL && (M + 320) * N * 4 < 0x7fffffffL;
 }
 
@@ -200,16 +234,25 @@ bool launch_rows_as(const float* a, const float* w, const float* bias, float* ds
     return true;
 }
 
+template <int WM>
+bool launch_rows_bf16(const float* a, const float* w, const float* bias, float* dst, const RowsShape& g, int relu, dim3 grid, hipStream_t st)
+{
+    typedef RowsCfg<false, WM, 1> C;                         // 31 KB | 43 KB: no opt-in needed
+    static_assert(C::LDS <= 64 * 1024, "fits the default dynamic LDS limit");
+    hipLaunchKernelGGL((linrows_bf16_kernel<WM>), grid, dim3(C::NT), C::LDS, st, a, w, bias, dst, g, relu);
+    return true;
+}
+
 }  // namespace
 
 // ---- what csrc/conv.hip takes from here (linrows.h) --------------------------------------------------------------------------------
 // Mode 1, the shapes this kernel was measured faster at than the generic one: many-row layers - never the
 // few-rows ones, which have kernels of their own - with whole column tiles, a deep reduction, a plan nobody forced, and a launch that
 // is one (nearly) full round of the CUs.
-int linrows_wm(long M, int K, int N, int splits)
+int linrows_wm(bool dgrad, long M, int K, int N, int splits)
 {
     const Tuning& tn = tuning();
-    if (!tn.linrows || !rows_ok(M, K, N)) return 0;
+    if (!tn.linrows || !rows_ok(dgrad, M, K, N)) return 0;
     const int wm = splits == 1 ? 2 : 1;                     // 320 rows unsplit, 160 where split-K multiplies the workgroups
     if (tn.linrows == 2) return wm;
     if (tn.force_bm || tn.force_kt || M <= 256 || M > 2048 || (N % R_TN) != 0 || K < 1024) return 0;
@@ -223,6 +266,10 @@ bool linrows_launch(bool dgrad, int wm, const float* a, const float* w, const fl
     const long tiles_m = cdiv(M, wm * R_FM * 32);
     const RowsShape g{(int)M, K, N, splits, k_per_split, (int)tiles_m};
     const dim3 grid((unsigned)(tiles_m * cdiv(N, R_TN)), 1, (unsigned)splits);
+    if (tuning().mma_mode == 4) {
+        if (dgrad) return false;                             // (never picked: linrows_wm)
+        return wm == 2 ? launch_rows_bf16<2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_bf16<1>(a, w, bias, dst, g, relu, grid, st);
+    }
     if (dgrad) return wm == 2 ? launch_rows_as<true, 2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_as<true, 1>(a, w, bias, dst, g, relu, grid, st);
     return wm == 2 ? launch_rows_as<false, 2>(a, w, bias, dst, g, relu, grid, st) : launch_rows_as<false, 1>(a, w, bias, dst, g, relu, grid, st);
 }

@@ -5,13 +5,15 @@
 
 struct Tuning {
     // ---- arithmetic and operand path of the GEMM kernels (conv.hip, conv_wgrad.hip, linear_bwd.hip) ----
-    int mma_mode = 3;            // 3: exact 3-term bf16 split at staging; 0: f32-input MFMA; 1 / 2: bf16 splits in registers (phnet_tune_mma)
-    int pf = 4;                  // register prefetch depth in K tiles (phnet_tune_mma sets 4 in mode 3, else 1; phnet_tune_force_k_tile(-101 / -102 / -104))
+    int mma_mode = 3;            // 3: exact 3-term bf16 split at staging; 0: f32-input MFMA; 1 / 2: bf16 splits in registers; 4: bf16 inference arithmetic, forward only (phnet_tune_mma)
+    int pf = 4;                  // register prefetch depth in K tiles (phnet_tune_mma sets 4 in modes 3 and 4, else 1; phnet_tune_force_k_tile(-101 / -102 / -104))
     int buf_loads = 1;           // buffer-load operand path where it applies (phnet_tune_force_k_tile(-200 / -201))
     int uniform_tap = 1;         // uniform-tap kernel variant (phnet_tune_force_k_tile(-1 / -2) = off / on)
     int taps3 = 1;               // three-taps 3x3 / stride-1 forward / dgrad kernel (phnet_tune_force_k_tile(-5 / -6) = off / on)
     int linrows = 1;             // tall-tile producer / consumer kernel for the many-row Linear layers (linrows.hip; phnet_tune_force_k_tile(-300 / -301) = off / on;
                                  // -302 = 2: for EVERY Linear launch without addend / statistics the kernel can run, whatever its size and the forced plan)
+    int bf16_splitk = 0;         // arithmetic mode 4 takes mode 3's split-K plan (phnet_tune_force_k_tile(-400 / -401) = off / on).  Off: mode 4 never
+                                 // splits K on its own, so that an output's bits do not depend on the batch size (DESIGN.md "bf16 inference")
     int deep_kt3 = 64;           // K tile of the few-rows GEMMs in mode 3 (phnet_tune_force_k_tile(-32 / -64))
     // ---- forced forward / dgrad plan (0 = heuristic) ----
     int force_bm = 0, force_bn = 0, force_splits = 0;       // phnet_tune_force_conv_tile

@@ -25,6 +25,7 @@ PHNET_API int phnet_tune_force_k_tile(int32_t kt)
     if (kt == -101 || kt == -102 || kt == -104) { t.pf = -kt - 100; return PHNET_OK; }
     if (kt == -200 || kt == -201) { t.buf_loads = -kt - 200; return PHNET_OK; }
     if (kt <= -300 && kt >= -302) { t.linrows = -kt - 300; return PHNET_OK; }
+    if (kt == -400 || kt == -401) { t.bf16_splitk = -kt - 400; return PHNET_OK; }
     if (kt != 0 && kt != 16 && kt != 32 && kt != 64) return PHNET_ERR_ARG;
     t.force_kt = kt;
     return PHNET_OK;
@@ -43,9 +44,9 @@ PHNET_API int phnet_tune_wgrad(int32_t allow_bm128, int32_t target_blocks)
 
 PHNET_API int phnet_tune_mma(int32_t mode)
 {
-    if (mode < 0 || mode > 3) return PHNET_ERR_ARG;
+    if (mode < 0 || mode > 4) return PHNET_ERR_ARG;
     tuning().mma_mode = mode;
-    tuning().pf = mode == 3 ? 4 : 1;                           // the staged-split loop runs with a 4-tile register ring
+    tuning().pf = (mode == 3 || mode == 4) ? 4 : 1;            // the staged loops (exact split, bf16 inference) run with a 4-tile register ring
     return PHNET_OK;
 }
 

@@ -141,9 +141,13 @@ class GraphedInference:
     frames [T,3,H,W]: one clip (RouterOL.infer_device); frames [B,T,3,H,W]: B clips per replay with the lane head
     batched across the clips (RouterOL.infer_clips_device).  polylines=True captures the lane-points launch as well
     (RouterOL.infer_points_device): `__call__` returns the same triple and `polylines` holds the device-resident points / count /
-    lanes_num / slot of the last replay (static graph buffers, like the triple)."""
+    lanes_num / slot of the last replay (static graph buffers, like the triple).  precision: "fp32" | "bf16", the arithmetic the
+    clip is captured in (INTEGRATION.md "bf16 inference")."""
 
-    def __init__(self, model: torch.nn.Module, frames: torch.Tensor, warmup: int = 2, polylines: bool = False):
+    def __init__(self, model: torch.nn.Module, frames: torch.Tensor, warmup: int = 2, polylines: bool = False, precision: str = "fp32"):
+        from . import hip_ops as K
+        K.precision_mode(precision, model.training)               # ValueError on an unknown name; "bf16" needs a model in eval()
+        self.precision = precision
         self.model = model.eval()
         self.frames = frames.clone()
         self.polylines = None
@@ -151,11 +155,12 @@ class GraphedInference:
             infer = model.infer_points_device
         else:
             infer = model.infer_clips_device if frames.dim() == 5 else model.infer_device
-        with torch.no_grad():
-            warm_up(lambda: infer(self.frames), warmup)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.out = infer(self.frames)
+        # warm-up and capture in the keyword's arithmetic; the captured launches keep it whatever the process mode is at replay
+        with torch.no_grad(), K.precision_scope(precision):
+            warm_up(lambda: infer(self.frames, precision=precision), warmup)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.out = infer(self.frames, precision=precision)
         if polylines:
             self.out, self.polylines = self.out[:3], self.out[3]
         torch.cuda.synchronize()

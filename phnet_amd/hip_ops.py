@@ -3,6 +3,7 @@
 PyTorch is used here only for device memory and the current HIP stream.  No op in this file has a
 fallback: a non-CUDA tensor or a missing library raises.
 """
+import contextlib
 import ctypes
 import os
 from typing import Optional, Tuple
@@ -174,20 +175,45 @@ def conv2d_fwd(x, w, bias, stride: int, pad: int, relu: bool = False, out: Optio
     return (out, (part, nblk)) if stats else out
 
 
+def _forward_only(what: str) -> None:
+    """The bf16 inference arithmetic has no backward: the library returns PHNET_ERR_ARG there, the wrappers say why."""
+    if mma_mode() == MMA_MODES["bf16"]:
+        raise RuntimeError(f'{what}: GEMM arithmetic mode "bf16" (phnet_tune_mma(4)) is forward-only; run the backward in the '
+                           f'default "bf16x3" arithmetic')
+
+
 def conv3p_applies(m: int, ca: int, nn: int) -> bool:
     return bool(lib().phnet_conv3p_applies(int(m), int(ca), int(nn)))
 
 
-def conv3p_pack(w: torch.Tensor, dgrad: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """w OHWI [Co,3,3,Ci] f32 -> the packed operand of conv3p (three bf16 planes in MFMA fragment order, csrc/conv3p.hip)."""
+def conv3p_planes() -> int:
+    """bf16 planes of the packed image phnet_conv3p_fwd takes in the current arithmetic: 1 in "bf16" (every weight rounded once), else 3."""
+    return 1 if mma_mode() == MMA_MODES["bf16"] else 3
+
+
+def conv3p_packed_bytes(co: int, ci: int, planes: int = 3) -> int:
+    assert planes in (1, 3), planes
+    return int(lib().phnet_conv3p_packed_bytes_bf16(co, ci) if planes == 1 else lib().phnet_conv3p_packed_bytes(co, ci))
+
+
+def conv3p_pack(w: torch.Tensor, dgrad: bool, out: Optional[torch.Tensor] = None, planes: Optional[int] = None) -> torch.Tensor:
+    """w OHWI [Co,3,3,Ci] f32 -> the packed operand of conv3p (bf16 planes in MFMA fragment order, csrc/conv3p.hip): three planes
+    (the exact split), or ONE (planes=1: the image of the "bf16" arithmetic, a third of the bytes, forward packing only).
+    planes=None: what the current arithmetic's conv3p takes."""
     _req(w, name="w")
     co, r, s_, ci = w.shape
     assert r == 3 and s_ == 3, w.shape
-    nbytes = int(lib().phnet_conv3p_packed_bytes(co, ci))
+    planes = conv3p_planes() if planes is None else planes
+    if planes == 1 and dgrad:
+        raise RuntimeError('conv3p_pack: the one-plane image of arithmetic mode "bf16" has no data-gradient packing (forward-only)')
+    nbytes = conv3p_packed_bytes(co, ci, planes)
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     assert out.numel() >= nbytes and out.is_contiguous()
-    check(lib().phnet_conv3p_pack(_ptr(w), _ptr(out), co, ci, int(dgrad), _stream()), "phnet_conv3p_pack")
+    if planes == 1:
+        check(lib().phnet_conv3p_pack_bf16(_ptr(w), _ptr(out), co, ci, _stream()), "phnet_conv3p_pack_bf16")
+    else:
+        check(lib().phnet_conv3p_pack(_ptr(w), _ptr(out), co, ci, int(dgrad), _stream()), "phnet_conv3p_pack")
     return out
 
 
@@ -196,11 +222,14 @@ class Conv3pPackPlan:
     (phnet_conv3p_pack_jobs): what a training step runs once before its first convolution.  The job table holds raw pointers:
     it is rebuilt when a weight has moved (`matches`)."""
 
-    def __init__(self, weights, with_dgrad: bool = True):
-        """weights: contiguous OHWI tensors [Co,3,3,Ci]."""
+    def __init__(self, weights, with_dgrad: bool = True, planes: int = 3):
+        """weights: contiguous OHWI tensors [Co,3,3,Ci].  planes=1: one-plane images of the "bf16" arithmetic (forward only)."""
         dev = weights[0].device
+        if planes == 1 and with_dgrad:
+            raise RuntimeError('Conv3pPackPlan: the one-plane images of arithmetic mode "bf16" are forward-only (with_dgrad=False)')
+        self.planes = planes
         self.ptrs = tuple(int(w.data_ptr()) for w in weights)
-        sizes = [int(lib().phnet_conv3p_packed_bytes(w.shape[0], w.shape[3])) for w in weights]
+        sizes = [conv3p_packed_bytes(w.shape[0], w.shape[3], planes) for w in weights]
         kinds = (False, True) if with_dgrad else (False,)
         self.buf = torch.empty(sum(sizes) * len(kinds), dtype=torch.uint8, device=dev)
         self.images, rows, off, first = [], [], 0, 0
@@ -224,15 +253,23 @@ class Conv3pPackPlan:
         return self.ptrs == tuple(int(w.data_ptr()) for w in weights)
 
     def refresh(self):
+        if self.planes == 1:
+            check(lib().phnet_conv3p_pack_jobs_bf16(_ptr(self.jobs), self.jobs.shape[0], self.total, _stream()), "phnet_conv3p_pack_jobs_bf16")
+            return
         check(lib().phnet_conv3p_pack_jobs(_ptr(self.jobs), self.jobs.shape[0], self.total, _stream()), "phnet_conv3p_pack_jobs")
 
 
 def conv3p(x: torch.Tensor, packed: torch.Tensor, nn: int, dgrad: bool = False, bias=None, addend=None, relu: bool = False,
            stats: bool = False):
     """3x3 / stride 1 / pad 1 convolution (dgrad=False) or its data gradient (dgrad=True: x = dy) on packed weights.
-    x NHWC [N,H,W,Ca] -> NHWC [N,H,W,nn]; stats as conv2d_fwd."""
+    x NHWC [N,H,W,Ca] -> NHWC [N,H,W,nn]; stats as conv2d_fwd.  In the "bf16" arithmetic `packed` is the one-plane image
+    (conv3p_pack(..., planes=1)) and there is no data gradient."""
     _req(x, name="x")
+    if dgrad:
+        _forward_only("conv3p(dgrad=True)")
     n, h, w_, ca = x.shape
+    planes = conv3p_planes()
+    assert packed.numel() >= 9 * ca * nn * 2 * planes, (packed.numel(), ca, nn, planes)
     out = torch.empty((n, h, w_, nn), dtype=torch.float32, device=x.device)
     m = n * h * w_
     need = splitk_workspace_bytes(m, nn)
@@ -249,13 +286,14 @@ def conv3p(x: torch.Tensor, packed: torch.Tensor, nn: int, dgrad: bool = False, 
                   lambda: check(lib().phnet_conv3p_fwd(_ptr(x), _ptr(packed), _ptr(bias), _ptr(addend), _ptr(out), _ptr(part), n, h, w_, ca, nn,
                                                        int(relu), _ptr(ws), need, _stream()), "phnet_conv3p_fwd"),
                   shape=("dgrad" if dgrad else "fwd", m, nn, 9 * ca, 3),
-                  nbytes=4.0 * m * (ca + nn) + 6.0 * 9 * ca * nn + (4.0 * m * nn if addend is not None else 0.0))
+                  nbytes=4.0 * m * (ca + nn) + 2.0 * planes * 9 * ca * nn + (4.0 * m * nn if addend is not None else 0.0))
     return (out, (part, nblk)) if stats else out
 
 
 def conv2d_dgrad(dy, w, in_hw: Tuple[int, int], stride: int, pad: int, addend: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None):
     _req(dy, name="dy"); _req(w, name="w")
+    _forward_only("conv2d_dgrad")
     n = dy.shape[0]
     co, r, s, ci = w.shape
     hi, wi = in_hw
@@ -279,6 +317,7 @@ def conv2d_wgrad(dy, x, w_shape, stride: int, pad: int, dw: Optional[torch.Tenso
     """dW (and, when `dbias` is given, the bias gradient = column sums of dy) in one launch (+ reduce when split).
     `accumulate` applies to both destinations."""
     _req(dy, name="dy"); _req(x, name="x")
+    _forward_only("conv2d_wgrad")
     n, hi, wi, ci = x.shape
     co, r, s, _ = w_shape
     if dw is None:
@@ -323,6 +362,7 @@ def linear_bwd(dy2d, x2d, w, dw: torch.Tensor, dbias: Optional[torch.Tensor], ac
     """dx = dy @ w and dw (+)= dy.T @ x (+ dbias) in one launch (few-rows Linear layers); returns dx.
     relu_y: saved output of a layer that ended in a ReLU - dy is masked by relu_y > 0 inside the kernel."""
     _req(dy2d, name="dy"); _req(x2d, name="x"); _req(w, name="w"); _req(dw, name="dw")
+    _forward_only("linear_bwd")
     m, n = dy2d.shape
     k = x2d.shape[1]
     dx = torch.empty((m, k), dtype=torch.float32, device=dy2d.device)
@@ -1748,8 +1788,11 @@ def tune_reset() -> None:
     check(lib().phnet_tune_reset(), "phnet_tune_reset")
 
 
+MMA_MODES = {"f32": 0, "split_bf16": 1, "split3_bf16": 2, "bf16x3": 3, "bf16": 4}
+
+
 def mma_mode() -> int:
-    """The library's current GEMM arithmetic (phnet_tune_mma code; 3 = "bf16x3")."""
+    """The library's current GEMM arithmetic (phnet_tune_mma code; 3 = "bf16x3", 4 = "bf16")."""
     return int(lib().phnet_tune_mma_get())
 
 
@@ -1759,5 +1802,46 @@ def set_mma_mode(mode: str) -> None:
     product, f32 accumulation (~4x the rounding noise of "f32"); "split3_bf16" = three bf16 terms (an exact split of the
     f32 value), 6 bf16 MFMAs per product, dropped terms <= 2^-24: the accuracy of "f32" (csrc/igemm.h); "bf16x3" = the same
     exact three-term arithmetic with the split done ONCE while a tile is staged into LDS (bf16 planes, transposed fragment
-    reads): the fast form of "split3_bf16"."""
-    check(lib().phnet_tune_mma({"f32": 0, "split_bf16": 1, "split3_bf16": 2, "bf16x3": 3}[mode]), "phnet_tune_mma")
+    reads): the fast form of "split3_bf16"; "bf16" = the inference arithmetic (forward only): every operand element rounded to
+    bf16 once while it is staged, one bf16 MFMA per product, f32 accumulation and epilogues (include/phnet_hip_tuning.h has the rule)."""
+    if mode not in MMA_MODES:
+        raise ValueError(f"unknown GEMM arithmetic {mode!r}: one of {sorted(MMA_MODES)}")
+    check(lib().phnet_tune_mma(MMA_MODES[mode]), "phnet_tune_mma")
+
+
+@contextlib.contextmanager
+def mma(mode: str):
+    """Runs the block in GEMM arithmetic `mode` (a set_mma_mode name) and puts the previous mode back, also when the block raises.
+    Only the arithmetic code is saved and restored, through phnet_tune_mma - which also gives the mode its register ring depth."""
+    if mode not in MMA_MODES:
+        raise ValueError(f"unknown GEMM arithmetic {mode!r}: one of {sorted(MMA_MODES)}")
+    before = mma_mode()
+    check(lib().phnet_tune_mma(MMA_MODES[mode]), "phnet_tune_mma")
+    try:
+        yield
+    finally:
+        check(lib().phnet_tune_mma(before), "phnet_tune_mma")
+
+
+PRECISIONS = {"fp32": "bf16x3", "bf16": "bf16"}
+
+
+def precision_mode(precision: str, training: bool = False) -> str:
+    """The set_mma_mode name behind the `precision` keyword of the inference entry points ("fp32" | "bf16")."""
+    if precision not in PRECISIONS:
+        raise ValueError(f'precision must be "fp32" or "bf16", not {precision!r}')
+    if precision == "bf16" and training:
+        raise RuntimeError('precision="bf16" is an inference arithmetic (forward-only): call model.eval() first')
+    return PRECISIONS[precision]
+
+
+@contextlib.contextmanager
+def precision_scope(precision: str, training: bool = False):
+    """`mma(...)` for the `precision` keyword.  "fp32" keeps whichever f32-accurate arithmetic the process is in - the entry points
+    behave as they did before the keyword existed, including under a mode a benchmark has set - and leaves only "bf16" for the default."""
+    mode = precision_mode(precision, training)
+    if precision == "fp32" and mma_mode() != MMA_MODES["bf16"]:
+        yield
+    else:
+        with mma(mode):
+            yield

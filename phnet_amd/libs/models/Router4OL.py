@@ -408,6 +408,24 @@ def _points_of(det, kept_rows: torch.Tensor, nums: torch.Tensor) -> dict:
     return {k: v.view(*lead, *v.shape[1:]) for k, v in out.items()}
 
 
+def precision_kw(fn):
+    """Gives an inference entry point the keyword precision="fp32" | "bf16": the call runs inside hip_ops.precision_scope, so the
+    conv / Linear GEMMs of the trunk, the neck and the head's Linear layers take that arithmetic and the process-wide mode is
+    afterwards what it was before.  ValueError on another name; "bf16" on a model in train() mode raises (forward-only arithmetic)."""
+    import functools
+
+    @functools.wraps(fn)
+    def with_precision(self, *args, precision: str = "fp32", **kwargs):
+        from phnet_amd import hip_ops as K
+        with K.precision_scope(precision, self.training):
+            return fn(self, *args, **kwargs)
+    import inspect
+    sig = inspect.signature(fn)                                   # (what help() and inspect show: fn's parameters + the keyword)
+    with_precision.__signature__ = sig.replace(parameters=[*sig.parameters.values(), inspect.Parameter(
+        "precision", inspect.Parameter.KEYWORD_ONLY, default="fp32", annotation=str)])
+    return with_precision
+
+
 class DeviceResults:
     """What a RouterOL of either family does with the device-resident results of its infer_device / infer_clips_device: to host
     lanes, to polylines, and the frame-at-a-time stream.  The model says where its lane head lives (`head`) and which class of
@@ -419,11 +437,12 @@ class DeviceResults:
         rows, n = kept_rows.cpu(), nums.cpu().tolist()
         return {"lane_lines": [self.head.predictions_to_pred(rows[t, :n[t]]) if n[t] else [] for t in range(len(n))]}
 
-    def infer_points_device(self, frames: torch.Tensor):
-        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]) plus the lanes as device-resident polylines:
+    def infer_points_device(self, frames: torch.Tensor, precision: str = "fp32"):
+        """infer_device (frames [T,3,H,W]) or infer_clips_device (frames [B,T,3,H,W]), in their `precision`, plus the lanes as device-resident polylines:
         returns (kept_rows, num, anchors, polylines), polylines = dict(points [..,max_lanes,S,2], count, lanes_num, slot) from one
         more launch over all frames (hip_ops.lane_points).  No host synchronisation (hipGraph-capturable)."""
-        rows, nums, anchors = (self.infer_device(frames) if frames.dim() == 4 else self.infer_clips_device(frames))[:3]
+        rows, nums, anchors = (self.infer_device(frames, precision=precision) if frames.dim() == 4
+                               else self.infer_clips_device(frames, precision=precision))[:3]
         return rows, nums, anchors, _points_of(self.head, rows, nums)
 
     def polylines_from_device(self, polylines: dict, kept_rows: torch.Tensor):
@@ -433,21 +452,24 @@ class DeviceResults:
         return P.to_host(polylines["points"], polylines["count"], polylines["lanes_num"], polylines["slot"], kept_rows)
 
     def open_stream(self, streams: int = 1, frame_hw=None, graph: bool = True, reset_every=None, raw=None, polylines: bool = False,
-                    track: bool = False, max_tracks=None, max_age=None, match_thres=None, render=None):
+                    track: bool = False, max_tracks=None, max_age=None, match_thres=None, render=None, precision: str = "fp32"):
         """Frame-at-a-time inference for `streams` live videos with the cross-frame memory kept on the device
         (phnet_amd.stream.LaneStream / LaneStreamV2: reset / step / lanes); one captured hipGraph serves every frame.
         polylines=True: the step also leaves the lanes' points on the device (stream.polylines, stream.lanes_fast()).
         track=True: the step also gives every kept row a stable id (stream.tracks; defaults: tracking.track_defaults).
-        render: a phnet_amd.overlay.LaneRenderer (with polylines=True) - the step also draws the lanes (stream.rendered)."""
+        render: a phnet_amd.overlay.LaneRenderer (with polylines=True) - the step also draws the lanes (stream.rendered).
+        precision: "fp32" | "bf16" - the arithmetic of the step's conv / Linear GEMMs; a captured step keeps it."""
         from phnet_amd import stream
         return getattr(stream, self.stream_class)(self, streams=streams, frame_hw=frame_hw, graph=graph, reset_every=reset_every,
                                                   raw=raw, polylines=polylines, track=track, max_tracks=max_tracks, max_age=max_age,
-                                                  match_thres=match_thres, render=render)
+                                                  match_thres=match_thres, render=render, precision=precision)
 
+    @precision_kw
     def track_clips(self, kept_rows: torch.Tensor, nums: torch.Tensor, max_tracks=None, max_age=None, match_thres=None):
         """Lane identities over the frames of a clip: kept_rows [T,max_lanes,6+S] / nums [T] of infer_device, or [B,T,..] / [B,T] of
         infer_clips_device -> (track_id, hits), int32 shaped like nums + (max_lanes,).  One hip_ops.lane_track launch on a fresh
-        tracking.TrackState per clip (defaults: tracking.track_defaults); no host synchronisation."""
+        tracking.TrackState per clip (defaults: tracking.track_defaults); no host synchronisation.  (precision= is accepted and checked
+        like on the infer_* calls whose rows this takes; the tracker itself runs no GEMM and computes the same in either.)"""
         from phnet_amd import hip_ops as K
         from phnet_amd.tracking import TrackState, track_defaults
         M, age, thr = track_defaults(self, max_tracks, max_age, match_thres)
@@ -573,6 +595,7 @@ class RouterOL(nn.Module, DeviceResults):
             det.priors = det.priors.detach()
             det.priors_on_featmap = det.priors_on_featmap.detach()
 
+    @precision_kw
     def infer_device(self, frame: torch.Tensor):
         """Eval forward of one clip without any host synchronisation (hipGraph-capturable): returns
         (kept_rows [T,max_lanes,6+S], num [T], anchors [T,max_lanes]) on the device."""
@@ -592,6 +615,7 @@ class RouterOL(nn.Module, DeviceResults):
         self._begin_clip()
         return torch.stack(rows), torch.stack(nums), torch.stack(anchors)
 
+    @precision_kw
     def infer_clips_device(self, frames: torch.Tensor):
         """Eval forward of B clips at once, frames [B,T,3,H,W]: the per-frame chain is serial only INSIDE a clip, so frame t of
         all clips runs through the lane head together (B*N rows per kernel instead of N - the head is launch-bound at N = 240).

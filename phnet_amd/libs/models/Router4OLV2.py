@@ -36,7 +36,7 @@ from ..utils.lane import Lane
 from .fpnV2 import FPN
 from .resnet import ResNetWrapper
 from .Router import AdaptiveRouter4LaneV2
-from .Router4OL import DetNetV2, DeviceResults, LinearModule
+from .Router4OL import DetNetV2, DeviceResults, LinearModule, precision_kw
 from .utils.dynamic_head import DynamicConvV2
 from .utils.transformer import TransformerDecoder, TransformerDecoderLayer
 
@@ -338,6 +338,7 @@ class RouterOL(nn.Module, DeviceResults):
             rows = torch.full_like(anchors_sorted, -1)
         return [K.memory_tokens(a.contiguous(), rows.contiguous()) for a in attn_feats]
 
+    @precision_kw
     def infer_device(self, frame: torch.Tensor):
         """Eval forward of one clip without host synchronisation (hipGraph-capturable).  Returns (kept_rows [T,max_lanes,6+S],
         num [T], anchors [T,max_lanes], aux) on the device; aux = per-frame lines / gates / stage outputs for the tests."""
@@ -364,6 +365,7 @@ class RouterOL(nn.Module, DeviceResults):
                 last_cuts.pop(0)
         return torch.stack(rows), torch.stack(nums), torch.stack(anchors), dict(frames=aux, gates=gate_rows)
 
+    @precision_kw
     @torch.no_grad()
     def infer_clips_device(self, frames: torch.Tensor):
         """Eval forward of B clips at once, frames [B,T,3,H,W]: the per-frame chain is serial only INSIDE a clip, so frame t of
@@ -391,10 +393,10 @@ class RouterOL(nn.Module, DeviceResults):
         return torch.stack(rows, dim=1), torch.stack(nums, dim=1), torch.stack(anchors, dim=1)
 
     @torch.no_grad()
-    def infer_points_device(self, frames: torch.Tensor):
+    def infer_points_device(self, frames: torch.Tensor, precision: str = "fp32"):
         """DeviceResults.infer_points_device under no_grad whoever calls, like infer_clips_device here (this family has no training
         path).  Not on the shared method: the V1 infer_* methods follow the caller's grad mode, which picks their branch kernels."""
-        return super().infer_points_device(frames)
+        return super().infer_points_device(frames, precision=precision)
 
     def forward(self, inputs: dict):
         frame, lanes = inputs.values()

@@ -115,11 +115,16 @@ class LaneStream:
     else on black.  What `step` returns does not change; without render= nothing is allocated, launched or returned differently.
 
     With graph=True the returned tensors (and `polylines`, `tracks`, `rendered`) are the graph's static outputs: the next `step`
-    overwrites them."""
+    overwrites them.
+
+    precision: "fp32" (default) or "bf16" - the arithmetic of the step's conv / Linear GEMMs (INTEGRATION.md "bf16 inference"); the
+    process-wide mode is what it was before, after the constructor and after every step."""
 
     def __init__(self, model, streams: int = 1, frame_hw: Tuple[int, int] = None, graph: bool = True, reset_every: Optional[int] = None,
                  raw=None, warmup: int = 2, polylines: bool = False, track: bool = False, max_tracks: Optional[int] = None,
-                 max_age: Optional[int] = None, match_thres: Optional[float] = None, render=None):
+                 max_age: Optional[int] = None, match_thres: Optional[float] = None, render=None, precision: str = "fp32"):
+        K.precision_mode(precision, model.training)               # ValueError on an unknown name; "bf16" needs a model in eval()
+        self.precision = precision
         if reset_every is not None and reset_every < 1:
             raise ValueError("reset_every must be a positive number of frames")
         if render is not None and not polylines:
@@ -154,10 +159,12 @@ class LaneStream:
         self.frame_index = 0                                      # host-side count of steps, for reset_every only
         self.graph, self.out = None, None
         if graph:
-            warm_up(lambda: self._body(self.frames), warmup)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = self._body(self.frames)
+            # the captured launches keep the arithmetic they were captured in, whatever the process mode is at replay
+            with K.precision_scope(precision):
+                warm_up(lambda: self._body(self.frames), warmup)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self.out = self._body(self.frames)
             torch.cuda.synchronize()
         self.reset()                                              # the warm-up frames are forgotten
         if self.track_state is not None:
@@ -219,7 +226,8 @@ class LaneStream:
             self.state.reset()
         self.frame_index += 1
         if self.graph is None:
-            return self._body(frames.contiguous())
+            with K.precision_scope(self.precision):
+                return self._body(frames.contiguous())
         self.frames.copy_(frames, non_blocking=True)
         self.graph.replay()
         return self.out

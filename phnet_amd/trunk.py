@@ -57,20 +57,24 @@ def _is3x3s1(conv: nn.Conv2d) -> bool:
 
 
 def packed_path() -> bool:
-    """The packed-weight 3x3 kernel (csrc/conv3p.hip) runs in the default GEMM arithmetic only."""
-    return K.CONV3P and K.mma_mode() == 3
+    """The packed-weight 3x3 kernel (csrc/conv3p.hip) runs in the default GEMM arithmetic and in the "bf16" inference arithmetic
+    (there on one-plane images: `K.conv3p_planes()`)."""
+    return K.CONV3P and K.mma_mode() in (3, 4)
 
 
 def _pack_plan(enc, convs):
     """Packed images (forward + data gradient) of every 3x3 / stride-1 weight of the encoder, refreshed by ONE launch per
-    training step; {id(conv): {False: forward image, True: dgrad image}}."""
+    training step; {id(conv): {False: forward image, True: dgrad image}}.  One plan per plane count: a forward under the "bf16"
+    arithmetic (one plane, no data-gradient image) never sees, and never replaces, the three-plane images."""
     weights = [ohwi(c.weight) for c in convs]
-    plan = enc.__dict__.get("_phnet_pack_plan")
+    planes = K.conv3p_planes()
+    key = "_phnet_pack_plan" if planes == 3 else "_phnet_pack_plan_bf16"
+    plan = enc.__dict__.get(key)
     if plan is None or not plan.matches(weights):
         if plan is not None:                                   # a captured hipGraph may still write the old images: retire, never free
             enc.__dict__.setdefault("_phnet_pack_retired", []).append(plan)
-        plan = K.Conv3pPackPlan(weights)
-        enc.__dict__["_phnet_pack_plan"] = plan
+        plan = K.Conv3pPackPlan(weights, with_dgrad=planes == 3, planes=planes)
+        enc.__dict__[key] = plan
     plan.refresh()
     return {id(c): img for c, img in zip(convs, plan.images)}
 
@@ -146,9 +150,12 @@ def weights_changed():
 def _folded(conv: nn.Conv2d, bn, w_ohwi: torch.Tensor):
     """(w * gamma / sqrt(var + eps) per output channel, beta - mean * gamma / sqrt(var + eps)) for an eval-mode conv -> BN pair.
     Cached ON the BatchNorm module (dies with the model), valid while no tensor version moved and no raw-pointer writer ran."""
-    ver = (_WEIGHT_EPOCH[0], packed_path(), conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
+    # (the arithmetic is part of the key: the packed image of "bf16" has one plane, the default's three - a model used in one
+    # mode and then in the other must never be handed the other mode's image)
+    ver = (_WEIGHT_EPOCH[0], packed_path(), K.mma_mode(), conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
            bn.running_var._version, conv.weight.data_ptr(), bn.running_mean.data_ptr(), w_ohwi.shape)
-    hit = bn.__dict__.get("_phnet_fold")
+    slot = "_phnet_fold_bf16" if K.mma_mode() == 4 else "_phnet_fold"      # one entry each: alternating precisions do not refold
+    hit = bn.__dict__.get(slot)
     if hit is not None and hit[0] == ver:
         return hit[1], hit[2], hit[3]
     with torch.no_grad():
@@ -156,7 +163,7 @@ def _folded(conv: nn.Conv2d, bn, w_ohwi: torch.Tensor):
         wf = (w_ohwi.reshape(w_ohwi.shape[0], -1) * scale[:, None]).reshape(w_ohwi.shape).contiguous()
         bf = (bn.bias.detach() - bn.running_mean * scale).contiguous()
         pk = K.conv3p_pack(wf, False) if (_is3x3s1(conv) and packed_path() and w_ohwi.shape[1] == 3) else None
-    bn.__dict__["_phnet_fold"] = (ver, wf, bf, pk)
+    bn.__dict__[slot] = (ver, wf, bf, pk)
     return wf, bf, pk
 
 
