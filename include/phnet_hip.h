@@ -597,7 +597,12 @@ int phnet_dwconv3x3_wgrad(const float* dy, const float* x, float* dw, float* db,
 /* ---- label assignment: replaces dynamic_assign.assign + scipy linear_sum_assignment on a .cpu() copy
  * (libs/utils/dynamic_assign.py:128-190) with one device launch.  pred [N][6+S], tgt [L][6+S] (col 1 == 1 = valid),
  * N <= 256, L <= 4.  rows_by_col [L] i64 (anchor matched to label j, -1 = none), rows_sorted [L] i64 (matched anchors
- * ascending, -1 padded), n_valid (optional) i32, cost (optional) [N][L] f32 (the solver's matrix, +inf = invalid). ---- */
+ * ascending, -1 padded), n_valid (optional) i32, cost (optional) [N][L] f32 (the solver's matrix, +inf = invalid).
+ * PRECONDITION: N >= the number of valid label rows.  The flags are device data, so the host cannot reject a violation;
+ * the kernels then report NO match at all (every row -1, n_valid 0, no pairs; the cost is still written) and the criteria
+ * below reduce to their classification terms - the same holds for every entry point that assigns (the three here,
+ * phnet_clip_loss / phnet_frame_loss, phnet_frame_loss_variant).  A one-to-many round that finds fewer unretired anchors than
+ * valid label rows ends the rounds the same way, keeping the pairs of the rounds before it. ---- */
 int phnet_lane_assign(const float* pred, const float* tgt, int32_t N, int32_t L, int32_t S,
                       float img_w, float img_h, int64_t* rows_by_col, int64_t* rows_sorted,
                       int32_t* n_valid, float* cost, void* stream);

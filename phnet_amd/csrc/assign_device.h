@@ -400,7 +400,9 @@ __device__ __forceinline__ void lane_assign_block(
             if (v < bv || (v == bv && c < bi)) { bv = v; bi = c; }
         }
         wave_arg_best<true>(bv, bi);
-        if (tid == 0) best_combo = bi;
+        // every combination invalid (fewer free anchors than valid label rows): no match at all, not combination 0, whose
+        // columns would share an anchor.  With no valid label, combination 0 is valid and costs 0.
+        if (tid == 0) best_combo = bv < INFINITY ? bi : 0x7fffffff;
     }
     __syncthreads();
     if (tid == 0) {
